@@ -3,10 +3,14 @@
 RCCL gradient all-reduce for N > 1, SGD step) on synthetic 473x473 RGB-D frame pairs,
 batch 4 per GPU, bf16 compute (BASELINE.json configs[1]; configs[2] when launched on 8 GPUs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0).  value = frame pairs per second over all ranks.
+Prints ONE JSON line (rank 0).  value = frame pairs per second over all ranks, ms_per_step = the
+wall time of one of the K timed steps.  A plain run sets up, warms up, times the K steps and
+prints the line; --dump-outputs DIR also writes what the last timed step produced as DIR/*.npy
+(same arguments -> same inputs, so two builds can be compared output for output).  Everything
+below is measured only with --full, after the timed steps:
 roofline: the implicit-GEMM MFMA kernel (every conv / linear / bmm of the step): algorithmic
 FLOPs (2*M*N*K per launch) / measured launch time (HIP events on the launch stream over the
 timed steps), against the 2.5 PFLOP/s dense bf16 MFMA peak of MI355X.
@@ -117,7 +121,47 @@ def parse():
                          "(parallelism dp1-chain-rccl)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group plumbing only (no model, no GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement: the roofline "
+                         "fields, the fp32 / fp8 extra lines, the configs[3] co-attention timing "
+                         "and the CPU baseline (each still under its own switch above); a plain "
+                         "run times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (its loss and both "
+                         "predictions) as DIR/<name>.npy (float32, at most 64 MB, rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.cpu_baseline = args.fp32_extra = args.fp8_extra = 0
+        args.no_roofline = True
+    return args
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, step, loss):
+    """--dump-outputs: what a caller of the timed step receives from its last call -- the loss it
+    returned (loss.npy) and the two predictions behind it (pred_a.npy, pred_b.npy, [B, 1, H, W];
+    the recorded program keeps them, an eager or one-graph step does not: then the loss alone).
+    The last step's predictions come out of the weights every earlier step updated, so they cover
+    the backward and SGD of the steps before it.  float32; predictions that would exceed
+    DUMP_MAX_BYTES are cut to a seeded sample of their elements (the same indices every run)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    out = {"loss": loss.detach().reshape(())}
+    x = (getattr(step, "_rec_env", None) or {}).get("x")
+    if x is not None:
+        out["pred_a"], out["pred_b"] = x[0].detach(), x[1].detach()
+    budget = (DUMP_MAX_BYTES - 4) // 8   # float32 elements per prediction
+    gen = torch.Generator(device="cpu").manual_seed(20260)
+    for name, t in out.items():
+        if t.numel() > budget:
+            idx = torch.randint(t.numel(), (budget,), generator=gen)
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 def pmc_traffic(family):
@@ -508,6 +552,8 @@ def main():
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:   # before anything below runs another step
+        dump_outputs(args.dump_outputs, step, loss)
     pairs = B * world * args.steps
     out = {
         "metric": "frame-pairs/sec (fwd+bwd) at 473x473 RGBD",

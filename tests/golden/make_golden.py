@@ -296,6 +296,12 @@ def main():
     meta["state_dict"] = [[k, list(v.shape), str(v.dtype)] for k, v in sd.items()]
     meta["init_seed0"] = {k: [float(v.double().sum()), float(v.double().abs().sum()),
                               float(v.flatten()[0])] for k, v in sd.items()}
+    # the sums above depend on the summation order (torch's thread count / vector width on the
+    # host that runs them); the crc32 of each tensor's bytes pins every bit on any host (a file
+    # of its own, one value per entry in state_dict order, 8 per line)
+    crc = [str(zlib.crc32(v.contiguous().numpy().tobytes())) for v in sd.values()]
+    with open(os.path.join(HERE, "init_seed0_crc32.json"), "w") as f:
+        f.write("[\n" + ",\n".join(" " + ", ".join(crc[i:i + 8]) for i in range(0, len(crc), 8)) + "\n]\n")
 
     # ---- 4. compute_iou known answers (evaluation.py:3-22) -----------------------------
     rng = np.random.RandomState(5)

@@ -124,6 +124,21 @@ def _bench_json(out):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_skips_side_measurements(monkeypatch):
+    """A plain bench run times its steps only; --full turns every side measurement back on
+    (each still under its own switch)."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 1, False, None)
+    assert a.no_roofline and not (a.cpu_baseline or a.fp32_extra or a.fp8_extra)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--fp8-extra", "0", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and not a.no_roofline and a.cpu_baseline and a.fp32_extra and not a.fp8_extra
+    assert a.dump_outputs == "d"
+
+
 def test_bench_gpus_n_spawns_n_ranks():
     """`bench.py --gpus 2` (no WORLD_SIZE: the driver's BENCH command shape) starts a child
     torch.distributed.run with 2 ranks and relays rank 0's single JSON line

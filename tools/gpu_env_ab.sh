@@ -9,7 +9,7 @@ mkdir -p $O
 for i in $(seq 1 $R); do
   for side in A B; do
     if [ $side = A ]; then E=$A; else E=$B; fi
-    env $E timeout -k 10 300 python bench.py --cpu-baseline 0 > $O/$side$i.json 2> $O/$side$i.err || { echo "bench $side$i failed" >> $O/summary.txt; exit 1; }
+    env $E timeout -k 10 300 python bench.py --full --cpu-baseline 0 > $O/$side$i.json 2> $O/$side$i.err || { echo "bench $side$i failed" >> $O/summary.txt; exit 1; }
     python3 -c "import json,sys; d=json.loads(open('$O/$side$i.json').read().strip().splitlines()[-1]); print('$side', '$E', d['value'], d['ms_per_step'])" >> $O/summary.txt
   done
 done

@@ -38,18 +38,18 @@ for step in "$@"; do
       timeout -k 10 600 $PY -m pytest -v --timeout 300 --timeout-method thread -m gpu "$arg" > $O/$tag.log 2>&1
       rc=$?; note "$step rc=$rc"; [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc ;;
     bench)
-      timeout -k 10 700 $PY bench.py ${arg//,/ } > $O/$tag.json 2> $O/$tag.err
+      timeout -k 10 700 $PY bench.py --full ${arg//,/ } > $O/$tag.json 2> $O/$tag.err
       rc=$?; note "$step rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     prof)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- \
-        python3 bench.py --steps 8 --warmup 3 --cpu-baseline 0 --fp32-extra 0 --fp8-extra 0 ${arg//,/ } > $O/prof.log 2>&1
+        python3 bench.py --full --steps 8 --warmup 3 --cpu-baseline 0 --fp32-extra 0 --fp8-extra 0 ${arg//,/ } > $O/prof.log 2>&1
       rc=$?; note "$step rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     envprof)
       # envprof:VAR=VALUE[,ARGS]  the prof step with one environment variable set (rocprofv3 takes
       # the program itself after --, so the variable is exported for this step only)
       ev=${arg%%,*}; rest=${arg#*,}; [ "$rest" = "$arg" ] && rest=""
       ( export "$ev"; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$i -o run -- \
-        python3 bench.py --steps 8 --warmup 3 --cpu-baseline 0 --fp32-extra 0 --fp8-extra 0 ${rest//,/ } > $O/prof_$i.log 2>&1 )
+        python3 bench.py --full --steps 8 --warmup 3 --cpu-baseline 0 --fp32-extra 0 --fp8-extra 0 ${rest//,/ } > $O/prof_$i.log 2>&1 )
       rc=$?; note "$step rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     pmc)
       timeout -k 10 600 bash tools/pmc_run.sh $O/pmc > $O/pmc.log 2>&1
@@ -63,7 +63,7 @@ for step in "$@"; do
     envbench)
       # envbench:VAR=VALUE,bench-args...  (one environment variable for an A/B bench line)
       ev=${arg%%,*}; rest=${arg#*,}
-      env "$ev" timeout -k 10 700 $PY bench.py ${rest//,/ } > $O/$tag.json 2> $O/$tag.err
+      env "$ev" timeout -k 10 700 $PY bench.py --full ${rest//,/ } > $O/$tag.json 2> $O/$tag.err
       rc=$?; note "$step rc=$rc"; [ $rc -eq 0 ] || exit $rc ;;
     *) note "unknown step $step"; exit 2 ;;
   esac

@@ -6,7 +6,7 @@ set -o pipefail
 mkdir -p gpurun_out/wt
 for i in 1 2; do
   for e in "X=0" "CN_GEMM_WT=1" "CN_BN_WT=1" "CN_GEMM_WT=1 CN_BN_WT=1"; do
-    env $e timeout -k 10 400 python bench.py --steps 20 --warmup 5 --cpu-baseline 0 --fp32-extra 0 --fp8-extra 0 2>/dev/null | python3 -c "
+    env $e timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --fp32-extra 0 --fp8-extra 0 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; c=d['roofline_coattention']
 print('$e', round(d['value'],2), 'ms/step %.2f gemm ev us %.1f | c3 %.1f us' % (d['ms_per_step'], r['event_avg_launch_us'], c['us_per_launch']))" | tee -a gpurun_out/wt/ab.txt || exit 1
   done
