@@ -104,6 +104,8 @@ _SIGS = {
     "cn_soft_iou": (_I, [_P, _P, _I, _L, _P, _P, _P, _P]),
     "cn_frame_resize": (_I, [_I, _P, _I, _L, _L, _L, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     "cn_gemm_force_config": (_I, [_I]),
+    "cn_gemm_ws_mode": (_I, [_I]),
+    "cn_gemm_ws_launches": (_S, []),
     "cn_gemm_set_wgrad_target": (_I, [_I]),
     "cn_coatt_force_variant": (_I, [_I]),
     "cn_head_fwd": (_I, [_I, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
@@ -152,9 +154,9 @@ def load():
     return lib
 
 
-HASHED_SOURCES = ["gemm.hip", "conv.hip", "bn.hip", "ew.hip", "coatt.hip", "coatt_fused.hip",
+HASHED_SOURCES = ["gemm.hip", "gemm_ws.hip", "conv.hip", "bn.hip", "ew.hip", "coatt.hip", "coatt_fused.hip",
                   "coatt_q48.hip", "coatt_flash.hip", "coatt_f8.hip", "fp8.hip", "frames.hip", "eval.hip",
-                  "common.h", "gemm.h", "coatt_fused.h", "../../include/cosnet_hip.h"]   # csrc/Makefile HASHED, same order
+                  "common.h", "gemm.h", "gemm_dev.h", "coatt_fused.h", "../../include/cosnet_hip.h"]   # csrc/Makefile HASHED, same order
 
 
 def source_hash():

@@ -85,5 +85,10 @@ long long cn_gemm_cfg_blocks(int cfg, int M, int N);
 // Tile rows (BM) of the configuration cn_gemm_dispatch uses for a problem (BN epilogues size
 // their per-M-tile partials with it).
 int cn_gemm_bm(int dtype, int M, int N, int K, int cfg_or_minus1);
+// Weight-stationary persistent kernel (gemm_ws.hip) for bf16 KC_DENSE x KC_DENSE products with
+// K in {64, 128, 256, 512}: shape / alignment conditions, and the launch.  `walkers_per_xcd` > 0
+// caps the M walkers of each XCD (0: as many as the CUs allow).
+bool cn_gemm_ws_supports(const GemmArgs& a);
+int cn_gemm_ws_launch(const GemmArgs& a, int walkers_per_xcd, hipStream_t st);
 int cn_splitk_reduce_impl(const float* ws, int nsplit, long long slab, long long n, float* out,
                           int accumulate, hipStream_t st);

@@ -18,6 +18,7 @@
 // K step = 128 bytes of k (64 bf16 / 32 fp32); register-staged double-buffered LDS.
 #include "common.h"
 #include "gemm.h"
+#include "gemm_dev.h"
 #include "../../include/cosnet_hip.h"
 
 #include <cstdlib>
@@ -48,22 +49,6 @@ __device__ __attribute__((aligned(16))) unsigned g_zero16[4];
 __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-// Buffer-descriptor form of the same LDS-DMA (buffer_load_dwordx4 ... lds): address = base +
-// soffset (SGPR, wave-uniform: the K position of the tile) + voffset (VGPR, constant per chunk
-// over a whole tap / the whole K loop).  The hardware range check covers voffset only (not
-// soffset): a chunk with no source (padding row / column, conv tap outside the image, k past the
-// end) gets voffset = BUF_OOB and reads zeros -- no zero page, no per-chunk select, no 64-bit
-// address arithmetic in the K loop.
-constexpr unsigned BUF_OOB = 0x80000000u;   // = num_records of every operand descriptor
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)BUF_OOB, 0x00020000);
-}
-__device__ __forceinline__ void blds16(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff,
-                                       char* lds_wave_base) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base,
-                                           16, (int)voff, (int)soff, 0, 0);
 }
 
 // -------------------------------------------------------------------------------------
@@ -373,15 +358,6 @@ __device__ __forceinline__ void wait_tiles(int n) {
   else if (n == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(G) : "memory");
   else if (n == 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * G) : "memory");
   else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * G) : "memory");
-}
-
-// Workgroup barrier that does NOT drain the LDS-DMA queue (unlike __syncthreads(), whose
-// fence emits vmcnt(0)); the asm memory clobbers keep the compiler from moving LDS accesses
-// across it.
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1332,6 +1308,36 @@ static int wt_on() {
   return lvl;
 }
 
+// Weight-stationary persistent kernel (gemm_ws.hip).  CN_GEMM_WS / cn_gemm_ws_mode: 0 off, 1 the
+// shape classes it was measured faster on (ws_heuristic), 2 every eligible problem, 3 as 2 with
+// one M walker per XCD (tests: long tile walks).
+static int g_ws_mode = -1;
+static size_t g_ws_launches = 0;
+static int ws_mode() {
+  if (g_ws_mode < 0) {
+    const char* e = getenv("CN_GEMM_WS");
+    const int v = e ? atoi(e) : 1;
+    g_ws_mode = (v >= 0 && v <= 3) ? v : 1;
+  }
+  return g_ws_mode;
+}
+// The measured classes (profiles/r07_gemm_ws_classes.txt): the bottlenecks' planes -> 4 planes
+// products of layers 1-3 and their dgrads (K 64 / 128 / 256 into N = 4 K, M >= 14400), each faster
+// in the recorded step than on the generic kernel.  K = 512 (layer 4) is slower on the new kernel
+// (its whole-K A stages leave room for a 32 x 64 tile only); the few narrower K = 256 products
+// (N = K, N = 2 K) share a trace class with the wide ones and stay on the generic kernel.
+static bool ws_heuristic(const GemmArgs& a) {
+  return a.K <= 256 && a.N >= 4 * a.K && a.M >= 8192;
+}
+static bool ws_eligible(const GemmArgs& a, int dtype, int c_f32, int la, int lb, int batch) {
+  if (!ws_mode() || g_force_cfg >= 0 || a.cfg >= 0) return false;
+  if (dtype != DT_BF16 || c_f32 || la != L_KC_DENSE || lb != L_KC_DENSE) return false;
+  if (batch != 1 || a.nsplit != 1 || a.row_map || a.ngroup || a.st_mode) return false;
+  if ((a.c_mode != 0 && a.c_mode != 2) || a.bias || a.alpha != 1.f || a.scale_a || a.scale_b) return false;
+  if (!cn_gemm_ws_supports(a)) return false;
+  return ws_mode() >= 2 || ws_heuristic(a);
+}
+
 int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb, int batch, hipStream_t st) {
   GemmArgs a = a_in;
   // per-block 32-bit offsets from the block's first row: not for the stride-2 row scatter
@@ -1344,6 +1350,10 @@ int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb,
   // pointer loader
   if (la == L_KC_CONV && (a.ga.C % bk != 0 || !buf_ok(L_KC_CONV, a, true, esz))) la = L_KC_CONV_G;
   if (!buf_ok(la, a, true, esz) || !buf_ok(lb, a, false, esz)) return CN_ERR_SHAPE;
+  if (ws_eligible(a, dtype, c_f32, la, lb, batch)) {
+    ++g_ws_launches;
+    return cn_gemm_ws_launch(a, ws_mode() == 3 ? 1 : 0, st);
+  }
   if (dtype == DT_FP8) {
     if (lb != L_KC_DENSE || a.nsplit != 1) return CN_ERR_UNSUPPORTED;
     if (a.st_mode && (a.st_mode != 1 || batch != 1 || a.row_map || a.c_mode || c_f32)) return CN_ERR_UNSUPPORTED;
@@ -1413,6 +1423,15 @@ extern "C" int cn_gemm_force_config(int cfg) {
   g_force_cfg = cfg;
   return kNumCfg;
 }
+
+extern "C" int cn_gemm_ws_mode(int mode) {
+  if (mode < 0 || mode > 3) return -1;
+  const int prev = ws_mode();
+  g_ws_mode = mode;
+  return prev;
+}
+
+extern "C" size_t cn_gemm_ws_launches(void) { return g_ws_launches; }
 
 // Split-K reduction: out[i] (+)= sum_s ws[s * slab + i]  (fp32, float4-vectorised).  A block
 // = (256 / G) float4 outputs x G slab groups: group g sums slabs g, g + G, ... (8 loads in

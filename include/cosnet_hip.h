@@ -445,6 +445,14 @@ int cn_build_experimental(void);
  * launch; -1 restores the shape heuristic.  Returns the number of configurations, or -1 for a
  * configuration this build does not carry (21-25 without EXPERIMENTAL=1). */
 int cn_gemm_force_config(int cfg);
+/* Development / test hook: routing of the weight-stationary persistent GEMM (csrc/gemm_ws.hip;
+ * bf16 1x1 products with K in {64, 128, 256, 512}).  0: off; 1: the shape classes it was measured
+ * faster on; 2: every eligible problem; 3: as 2 with one M walker per XCD (long tile walks).
+ * Returns the previous setting, or -1 for an unknown mode.  CN_GEMM_WS sets the default.  A
+ * configuration forced with cn_gemm_force_config takes precedence. */
+int cn_gemm_ws_mode(int mode);
+/* Launches routed to the weight-stationary kernel since the library was loaded (tests). */
+size_t cn_gemm_ws_launches(void);
 /* Development hook (tuning tools only): number of blocks the wgrad K split aims for. */
 int cn_gemm_set_wgrad_target(int blocks);
 /* Development / test hook: co-attention flash forward and PV kernel variant (1: four waves, one

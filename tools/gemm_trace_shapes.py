@@ -4,8 +4,10 @@ both encoder streams running as in the bench; no per-launch events).
     python tools/gemm_trace_shapes.py <run_kernel_trace.csv> [steps]
 
 A class = (tile / loader / epilogue template, grid): the grid gives ceil(M/BM) x ceil(N/BN) x
-batch*splits, the template the tile, so each class is one conv shape of the step.  Steps are
-delimited by the SGD launch; the last `steps` complete steps are averaged.
+batch*splits, the template the tile, so each class is one conv shape of the step.  The
+weight-stationary kernel (gemm_ws.hip) is its own class "ws k<K> BMxBN wWMxWN m<c_mode>"; its grid
+is 8 x walkers-per-XCD x column slices blocks, whatever M is.  Steps are delimited by the SGD
+launch; the last `steps` complete steps are averaged.
 """
 import csv
 import re
@@ -15,6 +17,13 @@ from collections import defaultdict
 
 def short(name):
     """T BMxBN wWMxWN sS L<LA><LB> e<EPI> p<PP> from the (mangled) template name."""
+    w = re.search(r"gemm_ws_kernel(?:I|<)(.*)", name)
+    if w:
+        a = re.findall(r"Li(\d+)E|Lb([01])E", w.group(1)) if "Li" in w.group(1) else []
+        v = [x or y for x, y in a] or re.findall(r"\d+|true|false", w.group(1))[:6]
+        if len(v) >= 6:
+            mode2 = v[5] in ("1", "true")
+            return "ws k%d %sx%s w%sx%s m%d" % (64 * int(v[0]), v[1], v[2], v[3], v[4], 2 if mode2 else 0)
     m = re.search(r"gemm_kernelI(.*?)Li(\d+)E", name)
     if not m:
         return name[:60]
@@ -35,7 +44,7 @@ def main(path, nsteps=4):
         for r in rows[a + 1:b + 1]:
             d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
             tot_all += d
-            if "gemm_kernel" not in r["Kernel_Name"]:
+            if "gemm_kernel" not in r["Kernel_Name"] and "gemm_ws_kernel" not in r["Kernel_Name"]:
                 continue
             wg = int(r["Workgroup_Size_X"])
             grid = (int(r["Grid_Size_X"]) // wg, int(r["Grid_Size_Y"]), int(r["Grid_Size_Z"]))
