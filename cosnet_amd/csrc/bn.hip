@@ -375,11 +375,14 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
   const int chunk = blockIdx.x * L.CB + tx;
   float qmax = 0.f;
   const float qinv = y8 ? qstate[1] : 0.f;
-  if (chunk >= L.CPR || ty >= L.RPB) {
-    if (y8) fp8_block_amax(qmax, qstate);
-    return;
-  }
-  const int seg = blockIdx.z, c0 = chunk * V;
+  // threads past the chunk columns / row groups do no rows.  With an fp8 copy they stay (channel
+  // 0's constants, an empty row range) and reach the ONE block-wide amax reduction below with the
+  // rest of their wave: a second call site on an early-exit path put a wave that holds both
+  // kinds of thread through two barriers, and thread 0 read that wave's maximum before it was
+  // written (256 % CB != 0, e.g. C = 320 in bf16).
+  const bool idle = chunk >= L.CPR || ty >= L.RPB;
+  if (idle && !y8) return;
+  const int seg = blockIdx.z, c0 = idle ? 0 : chunk * V;
   const long long row0 = (long long)seg * P;
   float sc[V], sf[V], rsc[V], rsf[V], t0[V], t1[V];
   ld_params<V>(gamma, c0, 1.f, sc);
@@ -404,7 +407,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
   }
   const float a = (act == 2) ? prelu[0] : 0.f;
   const int step = gridDim.y * L.RPB;
-  for (int r0 = blockIdx.y * L.RPB + ty; r0 < P; r0 += UNR * step) {
+  for (int r0 = idle ? P : blockIdx.y * L.RPB + ty; r0 < P; r0 += UNR * step) {
     float f[UNR][V], q[UNR][V];
     // all loads of the UNR rows issued unconditionally (rows past P re-read the segment's first
     // row and are not stored): no bounds branch between them

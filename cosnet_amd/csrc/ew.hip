@@ -825,6 +825,7 @@ extern "C" int cn_weight_prep(int dtype, const float* w, int Cout, int KHW, int 
 
 extern "C" int cn_maxpool_fwd(int dtype, const void* x, int N, int H, int W, int C, int OH, int OW,
                               int k, int s, int pad, void* y, unsigned char* argmax, hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   long long n = (long long)N * OH * OW * (C / (dtype == DT_BF16 ? 8 : 4));
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(maxpool_fwd_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, (const bf16*)x, N, H, W, C, OH, OW, k, s, pad, (bf16*)y, argmax);
@@ -837,6 +838,7 @@ extern "C" int cn_maxpool_fwd(int dtype, const void* x, int N, int H, int W, int
 extern "C" int cn_maxpool_bwd(int dtype, const void* dy, const unsigned char* argmax, int N, int H,
                               int W, int C, int OH, int OW, int k, int s, int pad, void* dx,
                               hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   long long n = (long long)N * H * W * (C / (dtype == DT_BF16 ? 8 : 4));
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(maxpool_bwd_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, (const bf16*)dy, argmax, N, H, W, C, OH, OW, k, s, pad, (bf16*)dx);
@@ -880,6 +882,7 @@ extern "C" int cn_avgpool(int dtype, const void* x, long long ld, int N, int HW,
 
 extern "C" int cn_bcast_rows(int dtype, const void* src, int N, int HW, int C, float scale,
                              void* dst, long long ld, int accumulate, hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   long long n = (long long)N * HW * (C / (dtype == DT_BF16 ? 8 : 4));
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(bcast_rows_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, (const bf16*)src, N, HW, C, scale, (bf16*)dst, ld, accumulate);
@@ -891,6 +894,7 @@ extern "C" int cn_bcast_rows(int dtype, const void* src, int N, int HW, int C, f
 
 extern "C" int cn_gate_fwd(int dtype, const void* z, long long ldz, int P, int C, const float* g,
                            const float* gb, void* out, long long ldo, float* mask, hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   dim3 grid((P + 3) / 4);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(gate_fwd_k<bf16>, grid, dim3(256), 0, st, (const bf16*)z, ldz, P, C, g, gb, (bf16*)out, ldo, mask);
@@ -972,6 +976,7 @@ extern "C" int cn_gate_bwd(int dtype, const void* z, long long ldz, const void* 
                            const float* mask, int P, int C, const float* g, int through_mask,
                            void* dz, long long lddz, float* dg, float* dgb, float* ws,
                            hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   if (C / (dtype == DT_BF16 ? 8 : 4) > 64) return CN_ERR_UNSUPPORTED;
   if ((dg || dgb) && !ws) return CN_ERR_SHAPE;
   int nb = rowpart_blocks(P);
@@ -990,6 +995,7 @@ extern "C" int cn_gate_bwd(int dtype, const void* z, long long ldz, const void* 
 extern "C" int cn_head_fwd(int dtype, const void* a, long long lda, const void* b, long long ldb,
                            int P, int C, int relu, const float* w, const float* bias, void* zout,
                            long long ldz, float* logit, hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   dim3 grid((P + 3) / 4);
   if (dtype == DT_BF16)
     hipLaunchKernelGGL(head_fwd_k<bf16>, grid, dim3(256), 0, st, (const bf16*)a, lda, (const bf16*)b, ldb, P, C, relu, w, bias, (bf16*)zout, ldz, logit);
@@ -1002,6 +1008,7 @@ extern "C" int cn_head_fwd(int dtype, const void* a, long long lda, const void* 
 extern "C" int cn_head_bwd(int dtype, const void* z, long long ldz, const float* dlogit, int P, int C,
                            int relu, const float* w, void* dz, long long lddz, float* dw, float* db,
                            float* ws, hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   if (C / (dtype == DT_BF16 ? 8 : 4) > 64) return CN_ERR_UNSUPPORTED;
   if ((dw || db) && !ws) return CN_ERR_SHAPE;
   int nb = rowpart_blocks(P);
@@ -1079,6 +1086,7 @@ extern "C" int cn_sgd(const void* tensors, int nt, const float* lrs, float wd, f
 
 extern "C" int cn_rowdot_seg(int dtype, const void* a, long long lda, const void* b, long long ldb,
                              int P, int C, int seg, int seg_ld, float* out, hipStream_t st) {
+  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
   if (seg < 1 || seg_ld < seg) return CN_ERR_SHAPE;
   dim3 grid((P + 3) / 4);
   if (dtype == DT_BF16)

@@ -743,7 +743,11 @@ def bn_apply(x, stats, bn, act=0, prelu=None, res=None, xr=None, rstats=None, rb
              nseg=1, out8=None, qstate=None, mask=None):
     """y = act(bn(x) [+ res] [+ rbn(xr)]) with per-segment statistics ([nseg*C] each); with
     out8 / qstate also an fp8 copy of y (delayed scaling, amax collected into qstate); with mask
-    (relu_mask) also y > 0 as bits, which bn_bwd(act=4) takes instead of y."""
+    (relu_mask) also y > 0 as bits, which bn_bwd(act=4) takes instead of y.
+
+    The fp8 copy (bf16 only; out8 row stride a multiple of 16) is quantised from the fp32 value of
+    the activation BEFORE its rounding to bf16: out8 = e4m3(clamp(t * qstate[1], +-448)) and
+    qstate[2] = max |t| with t the fp32 activation, so out8 is not the quantised stored y."""
     p, c = x.shape
     if out is None:
         out = torch.empty((p, c), dtype=x.dtype, device=x.device)
