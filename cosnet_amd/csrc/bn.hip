@@ -55,14 +55,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_rsrc(const void* base) {
 // output's base fit 31 bits: the lines go to memory as they are written instead of waiting dirty
 // in the XCD's L2 for the end-of-kernel write-back that the next kernel's start waits on
 // (+0.55 % on the step; the same for the GEMM epilogue's C stores measured -0.4 %:
-// profiles/r06_write_through_ab.txt).  CN_BN_WT=0: plain stores; 2: also the ReLU-mask bytes and
-// the fp8 output copy; 3: non-temporal (nt) stores instead (A/B runs).
-static int bn_wt_env() {
-  static const int lvl = [] { const char* e = getenv("CN_BN_WT"); return e ? atoi(e) : 1; }();
-  return lvl;
-}
+// profiles/r06_write_through_ab.txt; the same record has the rejected variants: the ReLU-mask
+// bytes and the fp8 output copy written through as well, and non-temporal stores instead).
 static int bn_wt(long long rows, long long ld, int esz) {
-  return rows * ld * esz < 0x7fff0000ll ? bn_wt_env() : 0;
+  return rows * ld * esz < 0x7fff0000ll ? 1 : 0;
 }
 
 // Column sums of the block's RPB rows of per-thread accumulators, written as
@@ -369,7 +365,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
                                                   int wt) {
   constexpr int V = VecOf<T>::N;
   // wt: y stored write-through (sc1), offsets from y (the host checked they fit 31 bits)
-  const __amdgpu_buffer_rsrc_t yrs = wt_rsrc(y), mkrs = wt_rsrc(mk), y8rs = wt_rsrc(y8);
+  const __amdgpu_buffer_rsrc_t yrs = wt_rsrc(y);
   const Layout L = layout_of<T>(C);
   const int tx = threadIdx.x % L.CB, ty = threadIdx.x / L.CB;
   const int chunk = blockIdx.x * L.CB + tx;
@@ -432,9 +428,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
         f[u][v] = t;
       }
       const u32x4 pk = Chunk<T>::pack(f[u]);
-      if (wt == 3)
-        __builtin_nontemporal_store(pk, (u32x4*)(y + r * ldy + c0));
-      else if (wt)
+      if (wt)
         __builtin_amdgcn_raw_buffer_store_b128(pk, yrs, (int)((r * ldy + c0) * (long long)sizeof(T)), 0, 16);
       else
         *(u32x4*)(y + r * ldy + c0) = pk;
@@ -444,10 +438,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
         unsigned bits = 0;
 #pragma unroll
         for (int v = 0; v < V; ++v) bits |= (sv[v] > 0.f ? 1u : 0u) << v;
-        if (wt == 2)
-          __builtin_amdgcn_raw_buffer_store_b8((unsigned char)bits, mkrs, (int)(r * ldm + chunk), 0, 16);
-        else
-          mk[r * ldm + chunk] = (unsigned char)bits;
+        mk[r * ldm + chunk] = (unsigned char)bits;
       }
       if (y8) {  // fp8 copy of the output for an fp8 consumer conv (delayed scaling)
 #pragma unroll
@@ -457,10 +448,7 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
           u32x2 o;
           o.x = pack4_fp8_bn(f[u][v] * qinv, f[u][v + 1] * qinv, f[u][v + 2] * qinv, f[u][v + 3] * qinv);
           o.y = pack4_fp8_bn(f[u][v + 4] * qinv, f[u][v + 5] * qinv, f[u][v + 6] * qinv, f[u][v + 7] * qinv);
-          if (wt == 2)
-            __builtin_amdgcn_raw_buffer_store_b64(o, y8rs, (int)(r * ldy8 + c0 + v), 0, 16);
-          else
-            *(u32x2*)(y8 + r * ldy8 + c0 + v) = o;
+          *(u32x2*)(y8 + r * ldy8 + c0 + v) = o;
         }
       }
     }
@@ -649,10 +637,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_k(const T* __restrict__ x, l
         o[v] = k1[v] * (dd - m1[v] - xh * m2[v]);
         d[u][v] = dd;
       }
-      if (wt == 3) {
-        __builtin_nontemporal_store(Chunk<T>::pack(o), (u32x4*)(dx + (long long)r * lddx + chunk * V));
-        if (dres) __builtin_nontemporal_store(Chunk<T>::pack(d[u]), (u32x4*)(dres + (long long)r * lddres + chunk * V));
-      } else if (wt) {
+      if (wt) {
         st_chunk_wt<T>(dxr, ((long long)r * lddx + chunk * V) * (long long)sizeof(T), o);
         if (dres) st_chunk_wt<T>(drr, ((long long)r * lddres + chunk * V) * (long long)sizeof(T), d[u]);
       } else {
@@ -850,9 +835,7 @@ extern "C" int cn_bn_apply_ex(int dtype, const void* x, long long ldx, int P, in
       !aligned16(rmean) || !aligned16(rinvstd) || !aligned16(rgamma) || !aligned16(rbeta))
     return CN_ERR_ALIGN;
   if (P < 1 || nseg < 1) return CN_ERR_SHAPE;
-  int wt = bn_wt((long long)nseg * P, ldy, dtype == DT_BF16 ? 2 : 4);
-  if (wt == 2 && ((mask && !bn_wt((long long)nseg * P, ldm, 1)) || (y8 && !bn_wt((long long)nseg * P, ldy8, 1))))
-    wt = 1;
+  const int wt = bn_wt((long long)nseg * P, ldy, dtype == DT_BF16 ? 2 : 4);
   int gx, gy;
   if (dtype == DT_BF16) {
     gy = grid_rows<bf16>(P, C, &gx, g_tune[T_AP_ROWS], g_tune[T_AP_BLOCKS], nseg);

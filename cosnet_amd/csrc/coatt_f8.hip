@@ -84,16 +84,12 @@ __device__ __forceinline__ float dec8(unsigned w, int sel) {
 }
 
 // ---- prepass: rows (Q / K images) ------------------------------------------------------------
+// (inference; training runs coatt_f8_prep_k below)
 // thread = (row, 32-channel block); rows >= HW of each batch entry are zero
-// bexp (training, coatt_f8_blkexp_k): the exponent of the row's 32 x 32 block instead of the
-// row segment's own; dq (training): the decoded MX values as bf16 (exact: 3 mantissa bits times
-// a power of two), the operand the flash backward recomputes S from.
 __global__ __launch_bounds__(256) void coatt_f8_rows_k(const bf16* __restrict__ x, long long ldx,
                                                        int B, int HW, int HWp,
                                                        unsigned char* __restrict__ x8,
-                                                       unsigned char* __restrict__ xs,
-                                                       const unsigned char* __restrict__ bexp,
-                                                       bf16* __restrict__ dq, long long lddq) {
+                                                       unsigned char* __restrict__ xs) {
   const long long t = blockIdx.x * 256ll + threadIdx.x;
   if (t >= (long long)B * HWp * 8) return;
   const int bi = (int)(t & 7);
@@ -108,15 +104,10 @@ __global__ __launch_bounds__(256) void coatt_f8_rows_k(const bf16* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 32; ++i) v[i] = 0.f;
   }
-  int e;
-  if (bexp) {
-    e = bexp[((long long)b * (HWp >> 5) + (r >> 5)) * 8 + bi];
-  } else {
-    float amax = 0.f;
+  float amax = 0.f;
 #pragma unroll
-    for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
-    e = e8m0_of(amax);
-  }
+  for (int i = 0; i < 32; ++i) amax = fmaxf(amax, fabsf(v[i]));
+  const int e = e8m0_of(amax);
   const float inv = ldexpf(1.f, 127 - e);
   u32x4 o0, o1;
   unsigned w[8];
@@ -130,45 +121,6 @@ __global__ __launch_bounds__(256) void coatt_f8_rows_k(const bf16* __restrict__ 
   *(u32x4*)dst = o0;
   *(u32x4*)(dst + 16) = o1;
   xs[prow * 8 + 4 * (bi & 1) + (bi >> 1)] = (unsigned char)e;
-  if (dq && r < HW) {
-    const float sc = ldexpf(1.f, e - 127);
-    bf16* dd = dq + ((long long)b * HW + r) * lddq + 32 * bi;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float f[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] = dec8(w[2 * q + (j >> 2)], j & 3) * sc;
-      *(u32x4*)(dd + 8 * q) = Chunk<bf16>::pack(f);
-    }
-  }
-}
-
-// Shared exponents for an operand used both as rows (S = Q K^T: blocks of 32 channels) and as V
-// (P V: blocks of 32 keys) -- Vb in training: one E8M0 exponent per 32 keys x 32 channels, so the
-// two MX images decode to the SAME values and the backward's single bf16 copy is the operand of
-// every product that read Vb.  One wave per block: lane -> key 2 x (lane >> 1) .. (16 channels).
-__global__ __launch_bounds__(256) void coatt_f8_blkexp_k(const bf16* __restrict__ x, long long ldx,
-                                                         int B, int HW, int nkb,
-                                                         unsigned char* __restrict__ bexp) {
-  const long long wv = blockIdx.x * 4ll + (threadIdx.x >> 6);
-  if (wv >= (long long)B * nkb * 8) return;
-  const int lane = threadIdx.x & 63;
-  const int cb = (int)(wv & 7);
-  const long long bk = wv >> 3;
-  const int kb = (int)(bk % nkb), b = (int)(bk / nkb);
-  const int key = kb * 32 + (lane >> 1);
-  float amax = 0.f;
-  if (key < HW) {
-    const bf16* src = x + ((long long)b * HW + key) * ldx + 32 * cb + 16 * (lane & 1);
-    float v[16];
-    Chunk<bf16>::unpack(*(const u32x4*)src, v);
-    Chunk<bf16>::unpack(*(const u32x4*)(src + 8), v + 8);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) amax = fmaxf(amax, fabsf(v[i]));
-  }
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  if (lane == 0) bexp[wv] = (unsigned char)e8m0_of(amax);
 }
 
 // ---- prepass: V^T tiles ------------------------------------------------------------------------
@@ -177,9 +129,7 @@ __global__ __launch_bounds__(256) void coatt_f8_blkexp_k(const bf16* __restrict_
 // i = (kk & 3) + 4 (kk >> 3), i.e. key(h, j) above
 __global__ __launch_bounds__(256) void coatt_f8_vt_k(const bf16* __restrict__ v, long long ldv, int B,
                                                      int HW, int nt, unsigned char* __restrict__ vt8,
-                                                     unsigned char* __restrict__ vts,
-                                                     const unsigned char* __restrict__ bexp, int nkb,
-                                                     bf16* __restrict__ dq, long long lddq) {
+                                                     unsigned char* __restrict__ vts) {
   const long long t = blockIdx.x * 256ll + threadIdx.x;
   if (t >= (long long)B * nt * 2 * D) return;
   const int d = (int)(t % D);
@@ -193,17 +143,11 @@ __global__ __launch_bounds__(256) void coatt_f8_vt_k(const bf16* __restrict__ v,
     const int key = tile * KT + 32 * u + kk;
     x[kk] = key < HW ? (float)v[((long long)b * HW + key) * ldv + d] : 0.f;
   }
-  int e;
-  if (bexp) {
-    e = bexp[((long long)b * nkb + 2 * tile + u) * 8 + (d >> 5)];
-  } else {
-    float amax = 0.f;
+  float amax = 0.f;
 #pragma unroll
-    for (int kk = 0; kk < 32; ++kk) amax = fmaxf(amax, fabsf(x[kk]));
-    e = e8m0_of(amax);
-  }
+  for (int kk = 0; kk < 32; ++kk) amax = fmaxf(amax, fabsf(x[kk]));
+  const int e = e8m0_of(amax);
   const float inv = ldexpf(1.f, 127 - e);
-  const float sc = ldexpf(1.f, e - 127);
   // half h gets keys kk with (kk >> 2) & 1 == h, at byte 16u + (kk & 3) + 4 (kk >> 3)
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
@@ -211,17 +155,8 @@ __global__ __launch_bounds__(256) void coatt_f8_vt_k(const bf16* __restrict__ v,
 #pragma unroll
     for (int i = 0; i < 16; ++i) y[i] = clampf8(x[(i & 3) + 8 * (i >> 2) + 4 * h] * inv);
     unsigned char* dst = vt8 + (bt * D + d) * KT + 32 * h + 16 * u;
-    const u32x4 pw = u32x4{pk4(y[0], y[1], y[2], y[3]), pk4(y[4], y[5], y[6], y[7]),
-                           pk4(y[8], y[9], y[10], y[11]), pk4(y[12], y[13], y[14], y[15])};
-    *(u32x4*)dst = pw;
-    if (dq) {   // decoded value of key kk = (i & 3) + 8 (i >> 2) + 4 h at channel d
-      const unsigned wd[4] = {pw.x, pw.y, pw.z, pw.w};
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int key = tile * KT + 32 * u + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (key < HW) dq[((long long)b * HW + key) * lddq + d] = (bf16)(dec8(wd[i >> 2], i & 3) * sc);
-      }
-    }
+    *(u32x4*)dst = u32x4{pk4(y[0], y[1], y[2], y[3]), pk4(y[4], y[5], y[6], y[7]),
+                         pk4(y[8], y[9], y[10], y[11]), pk4(y[12], y[13], y[14], y[15])};
   }
   vts[bt * 512 + u * 256 + (d & 31) * 8 + (d >> 5)] = (unsigned char)e;
 }
@@ -232,8 +167,8 @@ __global__ __launch_bounds__(256) void coatt_f8_vt_k(const bf16* __restrict__ v,
 // every MX image the forward reads plus the decoded bf16 copy the backward reads is written from
 // it:  op 0 = Va_t: row image, exponents per (row, 32 channels);  op 1 = Vb: row image AND V^T
 // image with one exponent per 32 keys x 32 channels;  op 2 = Va: V^T image, exponents per
-// (channel, 32 keys).  Same bytes as coatt_f8_rows_k / coatt_f8_vt_k / coatt_f8_blkexp_k (five
-// launches, ~84 us at 8 pairs) produce.
+// (channel, 32 keys).  It replaced five launches of row / V^T / block-exponent kernels (~84 us at
+// 8 pairs) that produced the same bytes.
 struct F8Prep {
   const bf16* x[3]; long long ldx[3];
   unsigned char* x8[2]; unsigned char* xs[2];        // row images of op 0, op 1
@@ -599,7 +534,7 @@ extern "C" int cn_coatt_f8_fwd(const void* vat, long long ld_vat, const void* va
 }
 
 extern "C" size_t cn_coatt_f8_train_workspace_bytes(int B, int HW) {
-  return cn_coatt_f8_workspace_bytes(B, HW) + (size_t)B * (hwq128(HW) / 32) * 8 + 256;
+  return cn_coatt_f8_workspace_bytes(B, HW);   // the prepass keeps its block exponents in LDS
 }
 
 extern "C" int cn_coatt_f8_train_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
@@ -636,8 +571,7 @@ static int f8_fwd(const void* vat, long long ld_vat, const void* va, long long l
   unsigned char* vtas = p;
   const long long nr = (long long)rows * 8;
   const dim3 gr((unsigned)((nr + 255) / 256));
-  static const bool prep5 = [] { const char* e = getenv("CN_F8_PREP5"); return e && e[0] == '1'; }();
-  if (train && !prep5) {   // one launch: all three operands' images and decoded copies
+  if (train) {   // one launch: all three operands' images and decoded copies
     F8Prep pa = {};
     pa.x[0] = (const bf16*)vat; pa.x[1] = (const bf16*)vb; pa.x[2] = (const bf16*)va;
     pa.ldx[0] = ld_vat; pa.ldx[1] = ld_vb; pa.ldx[2] = ld_va;
@@ -648,28 +582,15 @@ static int f8_fwd(const void* vat, long long ld_vat, const void* va, long long l
     hipLaunchKernelGGL(coatt_f8_prep_k, dim3((unsigned)(B * (HWp / 32)), 3), dim3(256), 0, st, pa);
     CN_CHECK_LAUNCH();
   } else {
-    unsigned char* bexp = nullptr;
-    if (train) {   // Vb's shared 32 x 32 block exponents (after the V^T scales, 256-aligned)
-      p = vtas + (size_t)B * nt * 512;
-      bexp = (unsigned char*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-      const long long nw = (long long)B * (HWp / 32) * 8;
-      hipLaunchKernelGGL(coatt_f8_blkexp_k, dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, st,
-                         (const bf16*)vb, ld_vb, B, HW, HWp / 32, bexp);
-      CN_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vat, ld_vat, B, HW, HWp, a8, as,
-                       (const unsigned char*)nullptr, (bf16*)vat_q, ld_q);
+    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vat, ld_vat, B, HW, HWp, a8, as);
     CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, HWp, b8, bs,
-                       (const unsigned char*)bexp, (bf16*)vb_q, ld_q);
+    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, HWp, b8, bs);
     CN_CHECK_LAUNCH();
     const long long nv = (long long)B * nt * 2 * D;
     const dim3 gv((unsigned)((nv + 255) / 256));
-    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, nt, vtb, vtbs,
-                       (const unsigned char*)bexp, HWp / 32, (bf16*)nullptr, 0ll);
+    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, nt, vtb, vtbs);
     CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)va, ld_va, B, HW, nt, vta, vtas,
-                       (const unsigned char*)nullptr, 0, (bf16*)va_q, ld_q);
+    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)va, ld_va, B, HW, nt, vta, vtas);
     CN_CHECK_LAUNCH();
   }
   F8Args a = {};

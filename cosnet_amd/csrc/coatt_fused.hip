@@ -24,7 +24,6 @@
 //     source address, so the DMA writes stay lane-linear.
 //   * O is rescaled only when some row's running max grew (wave-uniform branch, exact).
 #include "common.h"
-#include <cstdlib>
 #include "../../include/cosnet_hip.h"
 #include "coatt_fused.h"
 
@@ -394,7 +393,7 @@ void coatt_fused_fwd_k(FusedArgs a) {
 
 #if CN_EXPERIMENTAL
 // Measured-slower wave-pair variants (round 4): built only with CN_EXPERIMENTAL=1
-// (make EXPERIMENTAL=1), selected by cn_coatt_force_variant / CN_COATT_VARIANT in such builds.
+// (make EXPERIMENTAL=1), selected by cn_coatt_force_variant in such builds.
 // ---------------------------------------------------------------------------------------------
 // Two waves per SIMD (coatt_fused2_k): the same flash product, 8 waves = 4 wave PAIRS per
 // workgroup, 128 query rows.  Both waves of a pair hold the pair's 32 query rows in registers (Q,
@@ -1041,18 +1040,11 @@ static void plan_split(int items, int ntiles, int* nfull, int* nsplit) {
 // 4 = coatt_dsplit_k (coatt_dsplit.hip: wave pairs splitting the channels, 64 query rows per
 // pair), 5 = coatt_q48_k (coatt_q48.hip: 48 rows per wave, Q in registers, 16x16x32 tiles,
 // stream-K work split; the default since round 5: 183 vs 224 us at configs[3], 139 vs 165 us for
-// the training forward at 4 pairs, the PV kernel even).  CN_COATT_VARIANT picks the default;
-// cn_coatt_force_variant overrides it (tests, A/B tools).
+// the training forward at 4 pairs, the PV kernel even).  cn_coatt_force_variant overrides the
+// default (tests, A/B tools).
 static int g_coatt_variant = 0;
 static bool variant_built(int x) { return x == 1 || x == 5 || (CN_EXPERIMENTAL && x >= 2 && x <= 4); }
-static int coatt_variant() {
-  static const int v = [] {
-    const char* e = getenv("CN_COATT_VARIANT");
-    const int x = e ? atoi(e) : 5;
-    return variant_built(x) ? x : 5;
-  }();
-  return g_coatt_variant ? g_coatt_variant : v;
-}
+static int coatt_variant() { return g_coatt_variant ? g_coatt_variant : 5; }
 
 // Development / test hook: force the forward / PV kernel variant (1..5 as above; 0: default).
 // Returns the previous setting.
@@ -1062,13 +1054,6 @@ extern "C" int cn_coatt_force_variant(int v) {
   const int old = g_coatt_variant;
   g_coatt_variant = v;
   return old;
-}
-
-// The variant-5 launch of one co-attention call (coatt_q48.hip): work cut across the CUs when the
-// outputs take the merge's 16-byte rows (merge_ok) and the workspace holds the partials.
-static int q48_launch(int mode, FusedArgs& a, int B, int nd, bool merge_ok, void* ws,
-                      size_t ws_bytes, hipStream_t st) {
-  return coatt_q48_launch(mode, a, B, nd, merge_ok, ws, ws_bytes, st);
 }
 
 static int fused_launch(int mode, FusedArgs& a, int B, int nd, hipStream_t st) {
@@ -1081,8 +1066,8 @@ static int fused_launch(int mode, FusedArgs& a, int B, int nd, hipStream_t st) {
   const int nfull8 = (a.nfull + 7) & ~7;
   a.nwork = nfull8 + (a.nitems - a.nfull) * a.nsplit;
   dim3 grid(a.nwork);
-  const int var = coatt_variant();
 #if CN_EXPERIMENTAL
+  const int var = coatt_variant();
   if (var == 2) {
     if (mode == 0) hipLaunchKernelGGL(coatt_fused2_k<0>, grid, dim3(F2NT), 0, st, a);
     else hipLaunchKernelGGL(coatt_fused2_k<1>, grid, dim3(F2NT), 0, st, a);
@@ -1095,7 +1080,6 @@ static int fused_launch(int mode, FusedArgs& a, int B, int nd, hipStream_t st) {
   } else
 #endif
   {
-    (void)var;
     if (mode == 0) hipLaunchKernelGGL(coatt_fused_fwd_k<0>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(coatt_fused_fwd_k<1>, grid, dim3(256), 0, st, a);
   }
@@ -1131,50 +1115,14 @@ static int fused_check(const void* q, long long ldq, const void* k, long long ld
   return 0;
 }
 
-extern "C" int cn_coatt_fused_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
-                                  const void* vb, long long ld_vb, int B, int HW, int C, void* za,
-                                  void* zb, long long ld_z, hipStream_t st) {
-  return cn_coatt_flash_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, C, za, zb, ld_z, nullptr,
-                            nullptr, st);
-}
-
-extern "C" int cn_coatt_fused_fwd_ws(const void* vat, long long ld_vat, const void* va, long long ld_va,
-                                     const void* vb, long long ld_vb, int B, int HW, int C, void* za,
-                                     void* zb, long long ld_z, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (B <= 0 || HW <= 0) return CN_ERR_SHAPE;
-  int rc = fused_check(vat, ld_vat, vb, ld_vb, va, ld_va, ld_z, C);
-  if (rc) return rc;
-  if (((uintptr_t)za & 7) || ((uintptr_t)zb & 7)) return CN_ERR_ALIGN;
-  FusedArgs a = {};
-  int nd = 0;
-  if (za) a.dir[nd++] = FusedDir{(const bf16*)vat, (const bf16*)vb, (const bf16*)vb, (bf16*)za, ld_vat, ld_vb, ld_vb, ld_z, nullptr, nullptr};
-  if (zb) a.dir[nd++] = FusedDir{(const bf16*)vb, (const bf16*)vat, (const bf16*)va, (bf16*)zb, ld_vb, ld_vat, ld_va, ld_z, nullptr, nullptr};
-  if (nd == 0) return CN_ERR_SHAPE;
-  a.HW = HW;
-  a.HWp = (HW + 31) / 32 * 32;
-  // the merge writes 16-byte rows: unsplit when the outputs are not laid out for that
-  const bool merge_ok = !(((uintptr_t)za & 15) || ((uintptr_t)zb & 15) || (ld_z % 8));
-  if (coatt_variant() == 5) return q48_launch(0, a, B, nd, merge_ok, ws, ws_bytes, st);
-  const int nrb = (HW + FBQ - 1) / FBQ;
-  plan_split(nrb * B * nd, (HW + FBK - 1) / FBK, &a.nfull, &a.nsplit);
-  if (!merge_ok) a.nsplit = 1;
-  if (a.nsplit > 1) {
-    const size_t tail_rows = (size_t)a.nsplit * (nrb * B * nd - a.nfull) * FBQ;
-    // no (or a too small / misaligned) workspace: the unsplit launch, as the _ws siblings do
-    if (!ws || ws_bytes < tail_rows * (FD + 2) * sizeof(float) || !aligned16(ws)) {
-      a.nsplit = 1;
-    } else {
-      a.opart = (float*)ws;
-      a.mlpart = a.opart + tail_rows * FD;
-    }
-  }
-  return fused_launch(0, a, B, nd, st);
-}
-
-extern "C" int cn_coatt_flash_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
-                                  const void* vb, long long ld_vb, int B, int HW, int C, void* za,
-                                  void* zb, long long ld_z, float* lse_a, float* lse_b,
-                                  hipStream_t st) {
+// The forward of both directions (MODE 0), shared by the entry points below, which differ only
+// in the row statistics and the workspace they pass.  With a workspace that holds the partials
+// the work is cut across the CUs; without one (null, too small, misaligned) or with outputs the
+// merge's 16-byte rows do not fit, the launch runs unsplit.
+static int fused_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
+                     const void* vb, long long ld_vb, int B, int HW, int C, void* za, void* zb,
+                     long long ld_z, float* lse_a, float* lse_b, void* ws, size_t ws_bytes,
+                     hipStream_t st) {
   if (B <= 0 || HW <= 0) return CN_ERR_SHAPE;
   int rc = fused_check(vat, ld_vat, vb, ld_vb, va, ld_va, ld_z, C);
   if (rc) return rc;
@@ -1188,30 +1136,54 @@ extern "C" int cn_coatt_flash_fwd(const void* vat, long long ld_vat, const void*
   if (nd == 0) return CN_ERR_SHAPE;
   a.HW = HW;
   a.HWp = (HW + 31) / 32 * 32;
-  a.accumulate = 0;
-  if (coatt_variant() == 5) return q48_launch(0, a, B, nd, false, nullptr, 0, st);
+  // the merge writes 16-byte rows: unsplit when the outputs are not laid out for that
+  const bool merge_ok = !(((uintptr_t)za & 15) || ((uintptr_t)zb & 15) || (ld_z % 8));
+  if (coatt_variant() == 5) return coatt_q48_launch(0, a, B, nd, merge_ok, ws, ws_bytes, st);
+  const int nrb = (HW + FBQ - 1) / FBQ;
+  plan_split(nrb * B * nd, (HW + FBK - 1) / FBK, &a.nfull, &a.nsplit);
+  if (!merge_ok) a.nsplit = 1;
+  if (a.nsplit > 1) {
+    const size_t tail_rows = (size_t)a.nsplit * (nrb * B * nd - a.nfull) * FBQ;
+    if (!ws || ws_bytes < tail_rows * (FD + 2) * sizeof(float) || !aligned16(ws)) {
+      a.nsplit = 1;
+    } else {
+      a.opart = (float*)ws;
+      a.mlpart = a.opart + tail_rows * FD;
+    }
+  }
   return fused_launch(0, a, B, nd, st);
+}
+
+extern "C" int cn_coatt_fused_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
+                                  const void* vb, long long ld_vb, int B, int HW, int C, void* za,
+                                  void* zb, long long ld_z, hipStream_t st) {
+  return fused_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, C, za, zb, ld_z, nullptr, nullptr,
+                   nullptr, 0, st);
+}
+
+extern "C" int cn_coatt_fused_fwd_ws(const void* vat, long long ld_vat, const void* va, long long ld_va,
+                                     const void* vb, long long ld_vb, int B, int HW, int C, void* za,
+                                     void* zb, long long ld_z, void* ws, size_t ws_bytes, hipStream_t st) {
+  return fused_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, C, za, zb, ld_z, nullptr, nullptr, ws,
+                   ws_bytes, st);
+}
+
+extern "C" int cn_coatt_flash_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
+                                  const void* vb, long long ld_vb, int B, int HW, int C, void* za,
+                                  void* zb, long long ld_z, float* lse_a, float* lse_b,
+                                  hipStream_t st) {
+  return fused_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, C, za, zb, ld_z, lse_a, lse_b, nullptr,
+                   0, st);
 }
 
 extern "C" int cn_coatt_flash_fwd_ws(const void* vat, long long ld_vat, const void* va, long long ld_va,
                                      const void* vb, long long ld_vb, int B, int HW, int C, void* za,
                                      void* zb, long long ld_z, float* lse_a, float* lse_b, void* ws,
                                      size_t ws_bytes, hipStream_t st) {
-  if (coatt_variant() != 5)   // the 4-wave kernel runs the training forward unsplit
-    return cn_coatt_flash_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, C, za, zb, ld_z, lse_a, lse_b, st);
-  if (B <= 0 || HW <= 0) return CN_ERR_SHAPE;
-  int rc = fused_check(vat, ld_vat, vb, ld_vb, va, ld_va, ld_z, C);
-  if (rc) return rc;
-  if (((uintptr_t)za & 7) || ((uintptr_t)zb & 7)) return CN_ERR_ALIGN;
-  FusedArgs a = {};
-  int nd = 0;
-  if (za) a.dir[nd++] = FusedDir{(const bf16*)vat, (const bf16*)vb, (const bf16*)vb, (bf16*)za, ld_vat, ld_vb, ld_vb, ld_z, lse_a, nullptr};
-  if (zb) a.dir[nd++] = FusedDir{(const bf16*)vb, (const bf16*)vat, (const bf16*)va, (bf16*)zb, ld_vb, ld_vat, ld_va, ld_z, lse_b, nullptr};
-  if (nd == 0) return CN_ERR_SHAPE;
-  a.HW = HW;
-  a.HWp = (HW + 31) / 32 * 32;
-  const bool merge_ok = !(((uintptr_t)za & 15) || ((uintptr_t)zb & 15) || (ld_z % 8));
-  return q48_launch(0, a, B, nd, merge_ok, ws, ws_bytes, st);
+  // the 4-wave kernel runs the training forward unsplit
+  const bool split = coatt_variant() == 5;
+  return fused_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, C, za, zb, ld_z, lse_a, lse_b,
+                   split ? ws : nullptr, split ? ws_bytes : 0, st);
 }
 
 extern "C" int cn_coatt_flash_pv_ws(const void* q, long long ldq, const void* k, long long ldk,
@@ -1228,7 +1200,7 @@ extern "C" int cn_coatt_flash_pv_ws(const void* q, long long ldq, const void* k,
   a.HWp = (HW + 31) / 32 * 32;
   a.accumulate = accumulate;
   const bool merge_ok = !(((uintptr_t)o & 15) || (ldo % 8));
-  if (coatt_variant() == 5) return q48_launch(1, a, B, 1, merge_ok, ws, ws_bytes, st);
+  if (coatt_variant() == 5) return coatt_q48_launch(1, a, B, 1, merge_ok, ws, ws_bytes, st);
   const int nrb = (HW + FBQ - 1) / FBQ;
   plan_split(nrb * B, (HW + FBK - 1) / FBK, &a.nfull, &a.nsplit);
   if (!merge_ok) a.nsplit = 1;

@@ -15,9 +15,9 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 #define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
 
-// Measured-and-rejected kernel variants (co-attention wave pairs, GEMM tile configurations 21-25)
-// are compiled only into development builds (make EXPERIMENTAL=1); the product library keeps the
-// code that runs by default.
+// Measured-and-rejected co-attention kernel variants (wave pairs, variants 2-4) are compiled only
+// into development builds (make EXPERIMENTAL=1); the product library keeps the code that runs by
+// default.
 #ifndef CN_EXPERIMENTAL
 #define CN_EXPERIMENTAL 0
 #endif

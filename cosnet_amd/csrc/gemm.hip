@@ -21,7 +21,6 @@
 #include "gemm_dev.h"
 #include "../../include/cosnet_hip.h"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -393,18 +392,9 @@ __device__ __forceinline__ void wait_tiles(int n) {
 // kt-1 -- the phase whose lgkmcnt wait retired that group's last reads of tile kt-1 (a 2-stage
 // ring refills in the first phase instead, and retires the third phase's reads before its
 // barrier).
-//
-// PP == 2 (KSG, K-split wave groups; bf16 KC operands): 2 x WM x WN waves.  Group g (waves
-// g*WM*WN ..) runs k-piece g (32 of the tile's 64 k) of every K step on the WHOLE WM x WN tile
-// layout, i.e. each wave owns a wave tile twice the size it would have with 8 waves splitting the
-// block tile, and reads half as many fragments per MFMA: LDS fragment bytes per FLOP scale as
-// 1/TM + 1/TN (the DMA-write / ds_read contention the fill probe measures), while
-// two waves per SIMD remain.  The groups' partial accumulators are summed once, in the epilogue
-// (group 1 stages its tile in LDS, group 0 adds its own before the stores).
 template <class T, class CT, int BM, int BN, int WM, int WN, int S, int LA, int LB, int EPI = 0, int PP = 0>
-__global__ __launch_bounds__(WM * WN * 64 * (PP == 2 ? 2 : 1), (EPI && sizeof(T) == 2 && BM * BN <= 128 * 128 && S == 2) ? 4 : 1) void gemm_kernel(GemmArgs p) {
-  constexpr bool KSG = PP == 2;
-  constexpr int NT = WM * WN * 64 * (KSG ? 2 : 1);
+__global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 128 * 128 && S == 2) ? 4 : 1) void gemm_kernel(GemmArgs p) {
+  constexpr int NT = WM * WN * 64;
   constexpr int VEC = VecOf<T>::N;
   constexpr int BK = 8 * VEC;
   constexpr int ABYTES = BM * 128, BBYTES = BN * 128;
@@ -420,10 +410,7 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP == 2 ? 2 : 1), (EPI && sizeof(T)
   __shared__ __attribute__((aligned(16))) char smem[S * STAGE];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int kg = KSG ? wave / (WM * WN) : 0;            // KSG: this wave's k piece
-  const int wl = KSG ? wave % (WM * WN) : wave;
-  const int wm = wl / WN, wn = wl % WN;
-  static_assert(!KSG || (sizeof(T) == 2 && !AMC && !BMC), "KSG: bf16 k-contiguous operands");
+  const int wm = wave / WN, wn = wave % WN;
   // XCD-aware tile order (guide §5.5 T1, bijective form): blocks are dealt round-robin over
   // the 8 XCDs, so remap the linear id to give every XCD a contiguous run of M-tiles that
   // share the same B (weight) panel in its private L2.
@@ -531,7 +518,6 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP == 2 ? 2 : 1), (EPI && sizeof(T)
                    : ((BM / 2) * LDC * 4 <= S * STAGE) ? BM / 2
                    : ((BM / 4) * LDC * 4 <= S * STAGE) ? BM / 4 : BM / 8;
   static_assert(HR % 16 == 0 && HR * LDC * 4 <= S * STAGE, "epilogue staging must fit in the LDS image");
-  static_assert(!KSG || HR == BM, "KSG sums the two groups' tiles in one staging pass");
   constexpr int GPR = BN / 8;            // 8-column groups per row
   constexpr int RPP = NT / GPR;          // rows per pass
   constexpr int IT = HR / RPP;           // rows per thread per pass
@@ -626,8 +612,7 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP == 2 ? 2 : 1), (EPI && sizeof(T)
       return;
     }
 #pragma unroll
-    for (int pcl = 0; pcl < (KSG ? 1 : 2); ++pcl) {
-      const int pc = KSG ? kg : pcl;
+    for (int pc = 0; pc < 2; ++pc) {
       if constexpr (sizeof(T) == 2) {
         bf16x8 af[RM], bfr[RN];
 #pragma unroll
@@ -703,7 +688,7 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP == 2 ? 2 : 1), (EPI && sizeof(T)
         for (int j = 0; j < RN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
               af[i], bfr[j], acc[i][j], std::is_same<T, f8e5m2>::value ? 1 : 0, 0, 0, 127, 0, 127);
-    } else if constexpr (sizeof(T) == 2 && (AMC || BMC) && (RM + RN) <= 8 && !KSG) {
+    } else if constexpr (sizeof(T) == 2 && (AMC || BMC) && (RM + RN) <= 8) {
       // Transposed (MC) fragments are read with ds_read_b64_tr_b16, which hipcc cannot
       // disambiguate from an in-flight LDS-DMA: a DMA issued before these reads would cost a
       // full vmcnt(0) drain in front of them.  So read the whole tile's fragments FIRST, then
@@ -843,25 +828,15 @@ __global__ __launch_bounds__(WM * WN * 64 * (PP == 2 ? 2 : 1), (EPI && sizeof(T)
     }
     {
       const int g = lane >> 4;
-      // KSG: group 1 stages its partial tile, group 0 adds its own on top (one pass: HR == BM)
 #pragma unroll
-      for (int grp = 0; grp < (KSG ? 2 : 1); ++grp) {
-        if (!KSG || kg == 1 - grp) {
+      for (int i = 0; i < RM; ++i) {
+        const int rb = wm * TM + i * 16 - pass * HR;  // block's first row within this pass
+        if (rb < 0 || rb >= HR) continue;
 #pragma unroll
-          for (int i = 0; i < RM; ++i) {
-            const int rb = wm * TM + i * 16 - pass * HR;  // block's first row within this pass
-            if (rb < 0 || rb >= HR) continue;
+        for (int j = 0; j < RN; ++j)
 #pragma unroll
-            for (int j = 0; j < RN; ++j)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                float* c = &cs[(rb + 4 * g + r) * LDC + wn * TN + j * 16 + (lane & 15)];
-                if (KSG && grp == 1) *c += acc[i][j][r] * alpha;
-                else *c = acc[i][j][r] * alpha;
-              }
-          }
-        }
-        if (KSG && grp == 0) __syncthreads();
+          for (int r = 0; r < 4; ++r)
+            cs[(rb + 4 * g + r) * LDC + wn * TN + j * 16 + (lane & 15)] = acc[i][j][r] * alpha;
       }
     }
     __syncthreads();
@@ -1050,13 +1025,6 @@ static constexpr TileCfg kCfg[] = {
     {256, 128, 4, 2, 3, 1},  // 18: ping-pong, 8 waves of 64x64
     {128, 256, 2, 4, 3, 1},  // 19: ping-pong, 8 waves of 64x64
     {256, 256, 2, 4, 2, 1},  // 20: ping-pong, 8 waves of 128x64
-    // round 4: 4 waves (one per SIMD) with larger wave tiles -- fewer LDS fragment bytes per FLOP
-    // (1/TM + 1/TN), the contention the fill probe measures
-    {128, 256, 2, 2, 3},  // 21: 4 waves of 64x128
-    {256, 128, 2, 2, 3},  // 22: 4 waves of 128x64
-    {256, 256, 2, 2, 2},  // 23: (4 waves of 128x128 spill 36-151 VGPRs; launches config 10)
-    {128, 256, 1, 4, 3, 2},  // 24: KSG, 2 groups x 4 waves of 128x64
-    {128, 256, 2, 2, 3, 2},  // 25: KSG, 2 groups x 4 waves of 64x128
 };
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 static int g_force_cfg = -1;
@@ -1080,27 +1048,17 @@ static long long tiles_of(int c, int M, int N) {
 // (256x256, ASPP / layer-4 3x3: -2..-4 %) and the N = 256 frame-pair products with K >= 1024
 // (128x256: layer-3 3x3 fwd -7 %, 1x1 1024->256 fwd -9 %); 256x256 (8 waves of 64x128) also
 // takes the shallow N >= 1024 products (256->1024 fwd -7 %).  Transposed-operand (MC) products
-// picked for a ping-pong tile run its plain twin (launch_tile).  CN_GEMM_HEUR=1 selects the
-// round-2 rules (A/B runs).
+// picked for a ping-pong tile run its plain twin (launch_tile).
 static int heuristic_cfg(int M, int N, int K, int bz) {
-  static const int v1 = [] { const char* e = getenv("CN_GEMM_HEUR"); return e && e[0] == '1'; }();
   if (N <= 64) return 12;
-  if (v1) {
-    if (N >= 512 && K >= 2048 && tiles_of(10, M, N) * bz >= 200) return 10;
-    if (tiles_of(11, M, N) * bz <= 256 && K >= 512) return 13;
-    return 11;
-  }
   if (N >= 512 && K >= 2048 && tiles_of(10, M, N) * bz >= 200) return 20;
   if (tiles_of(11, M, N) * bz <= 256 && K >= 512) return 13;
-  // Round 4: 128x128 / 8 waves for these products (layer-3 3x3 fwd 38 vs 46 us, 1x1 fwd 22 vs 25
-  // us isolated; whole step +0.2 %: profiles/r04_gemm_n256_tiles_ab.txt).  CN_GEMM_N256 overrides
-  // it for A/B runs (19 = the round-3 128x256 ping-pong, 24 / 25 = K-split wave groups).
-  static const int n256 = [] { const char* e = getenv("CN_GEMM_N256"); const int v = e ? atoi(e) : 11; return (v >= 21 && !CN_EXPERIMENTAL) ? 11 : v; }();
-  if (N == 256 && K >= 1024 && tiles_of(19, M, N) * bz >= 200) return n256;
+  // Round 4: the N = 256, K >= 1024 products left the round-3 128x256 ping-pong tile for the
+  // default 128x128 / 8 waves below (layer-3 3x3 fwd 38 vs 46 us, 1x1 fwd 22 vs 25 us isolated;
+  // whole step +0.2 %: profiles/r04_gemm_n256_tiles_ab.txt).
   // shallow wide products (1x1 convs with K <= 512 into >= 1024 channels): 256x256 by the
-  // round-3 isolated sweep; CN_GEMM_SHALLOW overrides it for in-step A/B runs
-  static const int shallow = [] { const char* e = getenv("CN_GEMM_SHALLOW"); return e ? atoi(e) : 10; }();
-  if (N >= 1024 && K <= 512 && tiles_of(10, M, N) * bz >= 200) return shallow;
+  // round-3 isolated sweep
+  if (N >= 1024 && K <= 512 && tiles_of(10, M, N) * bz >= 200) return 10;
   return 11;
 }
 
@@ -1115,7 +1073,7 @@ static int launch_c(const GemmArgs& a, int batch, hipStream_t st) {
   constexpr TileCfg c = kCfg[C];
   dim3 grid((a.M + c.bm - 1) / c.bm, (a.N + c.bn - 1) / c.bn, batch * a.nsplit);
   hipLaunchKernelGGL((gemm_kernel<T, CT, c.bm, c.bn, c.wm, c.wn, c.s, LA, LB, EPI, c.pp>), grid,
-                     dim3(c.wm * c.wn * 64 * (c.pp == 2 ? 2 : 1)), 0, st, a);
+                     dim3(c.wm * c.wn * 64), 0, st, a);
   CN_CHECK_LAUNCH();
   return 0;
 }
@@ -1136,30 +1094,19 @@ static int launch_epi(const GemmArgs& a, int batch, hipStream_t st) {
       case 18: return launch_c<T, T, 18, LA, L_KC_DENSE, EPI>(a, batch, st);
       case 19: return launch_c<T, T, 19, LA, L_KC_DENSE, EPI>(a, batch, st);
       case 20: return launch_c<T, T, 20, LA, L_KC_DENSE, EPI>(a, batch, st);
-#if CN_EXPERIMENTAL
-      case 21: return launch_c<T, T, 21, LA, L_KC_DENSE, EPI>(a, batch, st);
-      case 22: return launch_c<T, T, 22, LA, L_KC_DENSE, EPI>(a, batch, st);
-      case 24: return launch_c<T, T, 24, LA, L_KC_DENSE, EPI>(a, batch, st);
-      case 25: return launch_c<T, T, 25, LA, L_KC_DENSE, EPI>(a, batch, st);
-#endif
       default: return CN_ERR_UNSUPPORTED;
     }
   }
 }
 
 // Read-add-store launches (c_mode 2, bf16 C: a dgrad accumulating into the residual gradient)
-// take the EPI 3 epilogue, whose old C rows are prefetched before the K loop.  CN_GEMM_PFC=0
-// keeps the plain epilogue (A/B runs).
-static bool pfc_on() {
-  static const bool on = [] { const char* e = getenv("CN_GEMM_PFC"); return !(e && e[0] == '0'); }();
-  return on;
-}
+// take the EPI 3 epilogue, whose old C rows are prefetched before the K loop.
 
 template <class T, class CT, int LA, int LB>
 static int launch_tile(const GemmArgs& a, int batch, hipStream_t st) {
   if constexpr (sizeof(T) == 2 && sizeof(CT) == 2 && (LA == L_KC_DENSE || LA == L_KC_CONV) &&
                 LB == L_KC_DENSE) {
-    if (a.c_mode == 2 && !a.row_map && !a.ngroup && pfc_on()) {
+    if (a.c_mode == 2 && !a.row_map && !a.ngroup) {
       switch (pick_cfg(a, batch)) {
         case 10: return launch_c<T, CT, 10, LA, LB, 3>(a, batch, st);
         case 11: return launch_c<T, CT, 11, LA, LB, 3>(a, batch, st);
@@ -1192,20 +1139,6 @@ static int launch_tile(const GemmArgs& a, int batch, hipStream_t st) {
       case 15: return launch_c<T, CT, 15, LA, LB>(a, batch, st);
       case 16: return launch_c<T, CT, 16, LA, LB>(a, batch, st);
       case 17: return launch_c<T, CT, 17, LA, LB>(a, batch, st);
-#if CN_EXPERIMENTAL
-      case 21: return launch_c<T, CT, 21, LA, LB>(a, batch, st);
-      case 22: return launch_c<T, CT, 22, LA, LB>(a, batch, st);
-      case 23: return launch_c<T, CT, 10, LA, LB>(a, batch, st);   // 4 waves of 128x128 spill: not built
-      case 24: case 25: {  // K-split wave groups: k-contiguous operands only
-        constexpr bool kc = LA != L_MC_DENSE && LA != L_MC_CONV && LB != L_MC_DENSE && LB != L_MC_CONV;
-        if constexpr (kc) {
-          if (pick_cfg(a, batch) == 24) return launch_c<T, CT, 24, LA, LB>(a, batch, st);
-          return launch_c<T, CT, 25, LA, LB>(a, batch, st);
-        } else {
-          return launch_c<T, CT, 11, LA, LB>(a, batch, st);
-        }
-      }
-#endif
       case 18: case 19: case 20: {  // ping-pong tiles: k-contiguous operands only
         constexpr bool kc = LA != L_MC_DENSE && LA != L_MC_CONV && LB != L_MC_DENSE && LB != L_MC_CONV;
         if constexpr (kc) {
@@ -1256,10 +1189,7 @@ static int launch_kinds(const GemmArgs& a, int la, int lb, int batch, hipStream_
 // three tiles the shape heuristic uses; 128 fp8 per 128-byte K tile, one scaled MFMA per tile.
 template <class CT, int LA, class T8 = f8e4m3>
 static int launch_f8(const GemmArgs& a, int batch, hipStream_t st) {
-  // (the 256x256 tile would spill its fp8 fragments: 128x128 serves the wide products too).
-  // Round 6: CN_GEMM_F8BIG = 8 (256x128) or 9 (128x256), 8 waves of 64x64 -- a quarter fewer LDS
-  // fill bytes per FLOP than 128x128 -- for the products with >= 256 such tiles (A/B runs).
-  static const int big = [] { const char* e = getenv("CN_GEMM_F8BIG"); return e ? atoi(e) : 0; }();
+  // (the 256x256 tile would spill its fp8 fragments: 128x128 serves the wide products too)
   const int c = pick_cfg(a, batch);
   if constexpr (sizeof(CT) == 2 && std::is_same<T8, f8e4m3>::value) {
     // fp8 conv forward with the BN-statistics epilogue (round 6; the bf16 path's EPI 1)
@@ -1270,10 +1200,6 @@ static int launch_f8(const GemmArgs& a, int batch, hipStream_t st) {
     }
   }
   if (a.st_mode) return CN_ERR_UNSUPPORTED;
-  if ((big == 8 || big == 9) && c != 12 && tiles_of(big, a.M, a.N) * batch >= 256) {
-    if (big == 8) return launch_c<T8, CT, 8, LA, L_KC_DENSE>(a, batch, st);
-    return launch_c<T8, CT, 9, LA, L_KC_DENSE>(a, batch, st);
-  }
   if (c == 12) return launch_c<T8, CT, 12, LA, L_KC_DENSE>(a, batch, st);
   if (c == 13) return launch_c<T8, CT, 13, LA, L_KC_DENSE>(a, batch, st);
   return launch_c<T8, CT, 11, LA, L_KC_DENSE>(a, batch, st);
@@ -1298,29 +1224,11 @@ static bool buf_ok(int kind, const GemmArgs& a, bool is_a, int esz) {
   return true;
 }
 
-// C store policy.  Default (CN_GEMM_WT=4): non-temporal (nt) stores of C -- the split-K slabs,
-// which the reduce kernel reads back, excepted -- +0.5 % on the step (profiles/r06_write_through_ab.txt:
-// the lines leave the L2 early instead of waiting dirty for the end-of-launch write-back).  A/B
-// variants: 0 plain stores; 1 write-through (sc1) for every C store (-0.4 %); 3 write-through for the
-// split-K slabs only (-1.4 %).
-static int wt_on() {
-  static const int lvl = [] { const char* e = getenv("CN_GEMM_WT"); return e ? atoi(e) : 4; }();
-  return lvl;
-}
-
-// Weight-stationary persistent kernel (gemm_ws.hip).  CN_GEMM_WS / cn_gemm_ws_mode: 0 off, 1 the
+// Weight-stationary persistent kernel (gemm_ws.hip).  cn_gemm_ws_mode: 0 off, 1 (default) the
 // shape classes it was measured faster on (ws_heuristic), 2 every eligible problem, 3 as 2 with
 // one M walker per XCD (tests: long tile walks).
-static int g_ws_mode = -1;
+static int g_ws_mode = 1;
 static size_t g_ws_launches = 0;
-static int ws_mode() {
-  if (g_ws_mode < 0) {
-    const char* e = getenv("CN_GEMM_WS");
-    const int v = e ? atoi(e) : 1;
-    g_ws_mode = (v >= 0 && v <= 3) ? v : 1;
-  }
-  return g_ws_mode;
-}
 // The measured classes (profiles/r07_gemm_ws_classes.txt): the bottlenecks' planes -> 4 planes
 // products of layers 1-3 and their dgrads (K 64 / 128 / 256 into N = 4 K, M >= 14400), each faster
 // in the recorded step than on the generic kernel.  K = 512 (layer 4) is slower on the new kernel
@@ -1330,19 +1238,25 @@ static bool ws_heuristic(const GemmArgs& a) {
   return a.K <= 256 && a.N >= 4 * a.K && a.M >= 8192;
 }
 static bool ws_eligible(const GemmArgs& a, int dtype, int c_f32, int la, int lb, int batch) {
-  if (!ws_mode() || g_force_cfg >= 0 || a.cfg >= 0) return false;
+  if (!g_ws_mode || g_force_cfg >= 0 || a.cfg >= 0) return false;
   if (dtype != DT_BF16 || c_f32 || la != L_KC_DENSE || lb != L_KC_DENSE) return false;
   if (batch != 1 || a.nsplit != 1 || a.row_map || a.ngroup || a.st_mode) return false;
   if ((a.c_mode != 0 && a.c_mode != 2) || a.bias || a.alpha != 1.f || a.scale_a || a.scale_b) return false;
   if (!cn_gemm_ws_supports(a)) return false;
-  return ws_mode() >= 2 || ws_heuristic(a);
+  return g_ws_mode >= 2 || ws_heuristic(a);
 }
 
 int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb, int batch, hipStream_t st) {
   GemmArgs a = a_in;
-  // per-block 32-bit offsets from the block's first row: not for the stride-2 row scatter
-  a.wt = wt_on() == 4 ? (a.c_mode != 1 && a.c_mode != 3 ? 4 : 0)
-                      : !a.row_map && a.c_mode != 1 && (wt_on() == 1 || (wt_on() == 3 && a.c_mode == 3));
+  // C store policy: non-temporal stores of C -- the atomics and the split-K slabs, which the
+  // reduce kernel reads back, excepted -- +0.5 % on the step over plain stores: the lines leave
+  // the L2 early instead of waiting dirty for the end-of-launch write-back.  Write-through (sc1)
+  // stores lost, for every C (-0.4 %) and for the slabs only (-1.4 %): profiles/r06_write_through_ab.txt
+  // The kernels keep the three store flavours of that A/B (0 plain, 4 non-temporal, other
+  // write-through): with the write-through branch compiled out the BN-backward epilogue of the
+  // 128x64 tile took 82-84 VGPRs instead of 77-79 and lost a block per CU, and the fp8 step stopped
+  // reproducing bitwise run to run (profiles/r08_retired_variants_ab.txt).
+  a.wt = a.c_mode != 1 && a.c_mode != 3 ? 4 : 0;
   if (a.M <= 0 || a.N <= 0 || batch <= 0) return 0;
   const int esz = (dtype == DT_FP8 || dtype == DT_FP8_E5M2) ? 1 : dtype == DT_BF16 ? 2 : 4;
   const int bk = 128 / esz;
@@ -1352,7 +1266,7 @@ int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb,
   if (!buf_ok(la, a, true, esz) || !buf_ok(lb, a, false, esz)) return CN_ERR_SHAPE;
   if (ws_eligible(a, dtype, c_f32, la, lb, batch)) {
     ++g_ws_launches;
-    return cn_gemm_ws_launch(a, ws_mode() == 3 ? 1 : 0, st);
+    return cn_gemm_ws_launch(a, g_ws_mode == 3 ? 1 : 0, st);
   }
   if (dtype == DT_FP8) {
     if (lb != L_KC_DENSE || a.nsplit != 1) return CN_ERR_UNSUPPORTED;
@@ -1419,14 +1333,14 @@ long long cn_gemm_cfg_blocks(int cfg, int M, int N) {
 
 // Development hook: force one tile configuration for every bf16 launch (-1 = heuristic).
 extern "C" int cn_gemm_force_config(int cfg) {
-  if (cfg >= kNumCfg || (!CN_EXPERIMENTAL && cfg >= 21)) return -1;
+  if (cfg >= kNumCfg) return -1;
   g_force_cfg = cfg;
   return kNumCfg;
 }
 
 extern "C" int cn_gemm_ws_mode(int mode) {
   if (mode < 0 || mode > 3) return -1;
-  const int prev = ws_mode();
+  const int prev = g_ws_mode;
   g_ws_mode = mode;
   return prev;
 }

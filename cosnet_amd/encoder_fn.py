@@ -70,11 +70,6 @@ ASPP_GROUPED = os.environ.get("CN_ASPP_GROUPED", "0") == "1"
 # step (the fp8 tiles' epilogue is long next to their K loop), so off by default;
 # CN_FP8_FUSE_STATS=1 selects it.
 FP8_FUSE_STATS = os.environ.get("CN_FP8_FUSE_STATS", "0") == "1"
-# TIMING PROBE ONLY (results are wrong): CN_PROBE_SKIP_APPLY=1 / 2 / 3 drops the bn1 / bn2 / both
-# BN + ReLU apply passes of every bottleneck (the next conv reads the raw conv output) -- the
-# upper bound of what folding those applies into the consumer conv's operand path could save
-# (VERDICT r4 "next" #4; profiles/r05_bn_fold_bound.txt).
-_PROBE_SKIP = int(os.environ.get("CN_PROBE_SKIP_APPLY", "0"))
 
 
 # The per-module path (functions.StemFn / BottleneckFn / ASPPFn: frames of different sizes, e.g.
@@ -350,12 +345,12 @@ def bottleneck_fwd(blk, x, geo, nseg, rec):
     w3f, w3t = WCACHE.get(blk.conv3.weight, dt)
     c1, oh, ow, st1 = conv_bn(x, n, h, w, w1f, planes, 1, s, 0, 1, blk.bn1, tr, nseg,
                               weight=blk.conv1.weight)
-    y1 = c1 if _PROBE_SKIP & 1 else seg_apply(c1, st1, blk.bn1, act=1, fp8_key=id(blk.conv2.weight))
+    y1 = seg_apply(c1, st1, blk.bn1, act=1, fp8_key=id(blk.conv2.weight))
     # the e4m3 input copy is kept for the backward only when the fp8 weight gradient reads it
     q2 = [] if rec is not None and WGRAD_FP8 else None
     c2, _, _, st2 = conv_bn(y1, n, oh, ow, w2f, planes, 3, 1, d, d, blk.bn2, tr, nseg,
                             weight=blk.conv2.weight, q8=q2)
-    y2 = c2 if _PROBE_SKIP & 2 else seg_apply(c2, st2, blk.bn2, act=1, fp8_key=id(blk.conv3.weight))
+    y2 = seg_apply(c2, st2, blk.bn2, act=1, fp8_key=id(blk.conv3.weight))
     c3, _, _, st3 = conv_bn(y2, n, oh, ow, w3f, 4 * planes, 1, 1, 0, 1, blk.bn3, tr, nseg,
                             weight=blk.conv3.weight)
     cd = std = wdt = None

@@ -438,17 +438,17 @@ int cn_frame_resize(int src_u8, const void* src, int C, long long plane_stride, 
  * compiled from (stamped by csrc/Makefile). */
 const char* cn_build_source_hash(void);
 /* 1 if the library was built with the development variants (make EXPERIMENTAL=1: co-attention
- * kernel variants 2-4, GEMM tile configurations 21-25), else 0. */
+ * kernel variants 2-4), else 0. */
 int cn_build_experimental(void);
 
 /* Development hook (tuning tools only): force GEMM tile configuration `cfg` for every bf16
- * launch; -1 restores the shape heuristic.  Returns the number of configurations, or -1 for a
- * configuration this build does not carry (21-25 without EXPERIMENTAL=1). */
+ * launch; -1 restores the shape heuristic.  Returns the number of configurations, or -1 (nothing
+ * changed) for an id that is not one of them. */
 int cn_gemm_force_config(int cfg);
 /* Development / test hook: routing of the weight-stationary persistent GEMM (csrc/gemm_ws.hip;
  * bf16 1x1 products with K in {64, 128, 256, 512}).  0: off; 1: the shape classes it was measured
  * faster on; 2: every eligible problem; 3: as 2 with one M walker per XCD (long tile walks).
- * Returns the previous setting, or -1 for an unknown mode.  CN_GEMM_WS sets the default.  A
+ * Returns the previous setting, or -1 for an unknown mode.  The default is 1.  A
  * configuration forced with cn_gemm_force_config takes precedence. */
 int cn_gemm_ws_mode(int mode);
 /* Launches routed to the weight-stationary kernel since the library was loaded (tests). */
@@ -461,7 +461,7 @@ int cn_gemm_set_wgrad_target(int blocks);
  * query rows that split the channels of S (partial S exchanged through LDS) and of the output;
  * 5: four waves of 48 query rows with Q in registers and a stream-K split of the key tiles over
  * the CUs -- the default; 0: default).  Returns the previous setting, or -1 for variants 2-4 in a
- * library built without them (cn_build_experimental() == 0).  CN_COATT_VARIANT sets the default. */
+ * library built without them (cn_build_experimental() == 0). */
 int cn_coatt_force_variant(int v);
 
 #ifdef __cplusplus

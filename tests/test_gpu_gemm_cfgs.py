@@ -3,8 +3,7 @@ cn_gemm_force_config) on the operand kinds the heuristic can route to it: conv f
 dense and 3x3 gathered loaders), stride-1 dgrad, the BN-statistics and BN-backward epilogues,
 and the weight gradient (transposed loaders; the ping-pong ids fall back there) -- against torch
 fp64, at shapes whose M, N and K all end in partial tiles.  The ping-pong tiles (ids 18-20)
-change the K loop's synchronisation (and 24-25, the K-split wave groups, sum two partial
-accumulators), so each is also run several times on the same inputs and
+change the K loop's synchronisation, so each is also run several times on the same inputs and
 must give bitwise-identical results (a fragment read racing an LDS-DMA fill shows up as
 run-to-run differences)."""
 import pytest
@@ -16,20 +15,13 @@ import test_gpu_kernels as K
 
 pytestmark = pytest.mark.gpu
 
-CFGS = [11, 13, 10, 15, 4, 18, 19, 20, 21, 22, 23, 24, 25]
-EPI_CFGS = {10, 11, 12, 13, 18, 19, 20, 21, 22, 24, 25}   # the tiles launch_epi instantiates
-
-
-EXPERIMENTAL_CFGS = {21, 22, 23, 24, 25}   # development builds only (make EXPERIMENTAL=1)
+CFGS = [11, 13, 10, 15, 4, 18, 19, 20]
+EPI_CFGS = {10, 11, 12, 13, 18, 19, 20}   # the tiles launch_epi instantiates
 
 
 @pytest.fixture
-def force_cfg(request):
+def force_cfg():
     lib = nv.load()
-    cfg = request.node.callspec.params.get("cfg") if hasattr(request.node, "callspec") else None
-    if cfg in EXPERIMENTAL_CFGS and not lib.cn_build_experimental():
-        assert lib.cn_gemm_force_config(cfg) == -1   # the product library refuses it
-        pytest.skip("tile configuration %d is built only with EXPERIMENTAL=1 (COSNET_HIP_LIB)" % cfg)
     yield lib.cn_gemm_force_config
     lib.cn_gemm_force_config(-1)
 
@@ -50,7 +42,7 @@ def test_conv_paths_per_config(cuda, force_cfg, cfg):
         K.test_conv_dgrad_bn_epilogue_reduce(cuda, bf, case)
 
 
-@pytest.mark.parametrize("cfg", [18, 19, 20, 24, 25])
+@pytest.mark.parametrize("cfg", [18, 19, 20])
 def test_ping_pong_tiles_are_deterministic(cuda, force_cfg, cfg):
     from cosnet_amd import ops
     force_cfg(cfg)
@@ -66,3 +58,34 @@ def test_ping_pong_tiles_are_deterministic(cuda, force_cfg, cfg):
     torch.cuda.synchronize()
     for y in outs[1:]:
         assert torch.equal(y, outs[0])
+
+
+def test_removed_variants_and_configs_are_refused(cuda):
+    """The tile configurations from 21 on were measured slower and removed, and the product
+    library does not carry the co-attention variants 2-4: both hooks answer -1 and change
+    nothing, so the heuristic still routes a 1x1 conv forward, which matches torch fp64."""
+    lib = nv.load()
+    if not lib.cn_build_experimental():
+        before = lib.cn_coatt_force_variant(1)
+        try:
+            for v in (2, 3, 4):
+                assert lib.cn_coatt_force_variant(v) == -1
+                assert lib.cn_coatt_force_variant(1) == 1   # the setting the refusal left behind
+        finally:
+            lib.cn_coatt_force_variant(before)
+    try:
+        ncfg = lib.cn_gemm_force_config(-1)
+        assert ncfg >= 21
+        assert lib.cn_gemm_force_config(21) == -1
+        assert lib.cn_gemm_force_config(ncfg) == -1
+        dt = torch.bfloat16
+        n, cin, h, w, cout = 1, 64, 9, 9, 64
+        x = K.rnd((n, cin, h, w), dt, 1)
+        wt = K.rnd((cout, cin, 1, 1), dt, 2, scale=(2.0 / cin) ** 0.5)
+        wp = wt.float().to(cuda).contiguous(memory_format=torch.channels_last)
+        wf, _ = K.ops.WCACHE.get(wp, dt)
+        y, _, _ = K.ops.conv_fwd(K.nhwc(x).to(dt).to(cuda).contiguous(), n, h, w, wf, cout, 1, 1, 0, 1)
+        torch.cuda.synchronize()
+        K.close(K.nchw(y, n, h, w), K.F.conv2d(x, wt), dt)
+    finally:
+        lib.cn_gemm_force_config(-1)
