@@ -40,6 +40,17 @@ __global__ void zero16_k(u32x4* p, long long n16) {
     p[i] = z;
 }
 
+// the same for the [rows][cpr] 16-byte chunks of a view whose rows are ld16 chunks apart
+__global__ void zero16_rows_k(u32x4* p, long long rows, int cpr, long long ld16) {
+  const u32x4 z = {0u, 0u, 0u, 0u};
+  const long long n16 = rows * cpr;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n16;
+       i += (long long)gridDim.x * blockDim.x) {
+    const long long r = i / cpr;
+    p[r * ld16 + (i - r * cpr)] = z;
+  }
+}
+
 extern "C" int cn_conv_fwd(int dtype, const void* x, long long ldx, int N, int H, int W, int Cin,
                            const void* w, int Cout, int KH, int KW, int stride, int pad, int dil,
                            const float* bias, void* y, long long ldy, int OH, int OW,
@@ -400,11 +411,15 @@ extern "C" int cn_conv_dgrad(int dtype, const void* dy, long long lddy, int N, i
   // 1x1 stride 2: only input pixels (2oy, 2ox) receive gradient; zero the rest first
   // (unless accumulating into an existing gradient).
   if (!accumulate) {
-    if (lddx != Cin) return CN_ERR_ALIGN;
-    long long n16 = (long long)N * H * W * Cin / vec_of(dtype);
-    if (((long long)Cin % vec_of(dtype)) || ((uintptr_t)dx & 15)) return CN_ERR_ALIGN;
+    const int vec = vec_of(dtype);
+    if (lddx < Cin || lddx % vec || Cin % vec || ((uintptr_t)dx & 15)) return CN_ERR_ALIGN;
+    long long n16 = (long long)N * H * W * Cin / vec;
     long long nb = (n16 + 255) / 256;
-    hipLaunchKernelGGL(zero16_k, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, st, (u32x4*)dx, n16);
+    if (lddx == Cin)
+      hipLaunchKernelGGL(zero16_k, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, st, (u32x4*)dx, n16);
+    else   // a channel slice of a wider buffer: only the view's [N*H*W][Cin] is zeroed
+      hipLaunchKernelGGL(zero16_rows_k, dim3(nb < 4096 ? nb : 4096), dim3(256), 0, st, (u32x4*)dx,
+                         (long long)N * H * W, Cin / vec, lddx / vec);
     CN_CHECK_LAUNCH();
   }
   a.M = N * OH * OW;

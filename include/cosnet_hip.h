@@ -30,6 +30,15 @@ extern "C" {
 #define CN_ERR_HIP (-4)
 
 /* ---- convolution / matrix products (implicit GEMM on MFMA) ---------------------------- */
+/* Rounding and bounds contract of cn_conv_fwd*, cn_conv_dgrad* and cn_gemm (tests/
+ * test_gpu_exact_gemm.py pins it bitwise on integer-valued operands):
+ *   - the output is ONE round-to-nearest-even rounding of the fp32 value
+ *     alpha * acc (+ bias) (+ old C), where alpha includes the fp8 dequantisation scales; a
+ *     split-K forward rounds after its reduce and the bias, an accumulating dgrad after the add
+ *   - nothing outside [M, N] of the output view (base, ld) is written
+ *   - no operand byte outside its view (base, ld) reaches the result: row padding and rows past
+ *     the last may hold anything, NaN included
+ *   (pinned on views with 16-byte aligned bases and ld % (4 fp32 | 8 bf16 | 16 fp8) == 0) */
 
 /* y = conv2d(x, w) + bias.  Replaces nn.Conv2d.forward for every conv of the path:
  * deeplab/residual_net.py:59,63-64,67,106,129 ; deeplab/deeplabv3_encoder.py:15,19,22-31 ;
@@ -50,7 +59,9 @@ int cn_conv_fwd_ws(int dtype, const void* x, long long ldx, int N, int H, int W,
                    size_t ws_floats, hipStream_t stream);
 
 /* dx = conv2d input-gradient (autograd of the calls above).  stride 1: any kernel;
- * stride 2: 1x1 / pad 0 only (deeplab/residual_net.py:59,129 of layer2 block 0). */
+ * stride 2: 1x1 / pad 0 only (deeplab/residual_net.py:59,129 of layer2 block 0); without
+ * `accumulate` the rows of the view that receive no gradient are zeroed (any lddx >= Cin).
+ * accumulate: dx = round(fp32(dx) + acc), one rounding. */
 int cn_conv_dgrad(int dtype, const void* dy, long long lddy, int N, int OH, int OW, int Cout,
                   const void* wt, int Cin, int KH, int KW, int stride, int pad, int dil,
                   void* dx, long long lddx, int H, int W, int accumulate, hipStream_t stream);
@@ -180,7 +191,8 @@ int cn_conv_dgrad_bn(int dtype, const void* dy, long long lddy, int N, int OH, i
                      float* sum_dzxh, float* ws, hipStream_t stream);
 
 /* Generic batched C = alpha * A . B^T (+bias) with per-operand layouts
- * (0 = k-contiguous rows, 2 = m/n-contiguous, k-major).  Replaces the linear + bmm calls of
+ * (0 = k-contiguous rows, 2 = m/n-contiguous, k-major; A / B are read as zero from k = ka_lim /
+ * kb_lim on, whatever the memory holds there).  Replaces the linear + bmm calls of
  * the co-attention: rgbd_segmentation_RAA.py:159-160,169-170 (RGB) and :212-213,220-221
  * (depth), and their autograd.  c_mode: 0 store, 1 fp32 atomic add, 2 accumulate,
  * 3 split-K slabs at C + split*slab (reduce with cn_splitk_reduce). */
