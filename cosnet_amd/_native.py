@@ -73,6 +73,9 @@ _SIGS = {
     "cn_coatt_fused_fwd": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P]),
     "cn_coatt_fused_fwd_ws": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _S, _P]),
     "cn_coatt_fused_workspace_bytes": (_S, [_I, _I, _I]),
+    "cn_coatt_fused_fwd_idx": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _I, _I, _I, _P, _P, _L, _P, _S, _P]),
+    "cn_gate_cat_idx": (_I, [_I, _P, _L, _P, _L, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
+    "cn_mean_groups": (_I, [_P, _I, _I, _I, _P, _P]),
     "cn_coatt_f8_workspace_bytes": (_S, [_I, _I]),
     "cn_coatt_f8_fwd": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _P, _P, _S, _P]),
     "cn_coatt_f8_train_workspace_bytes": (_S, [_I, _I]),

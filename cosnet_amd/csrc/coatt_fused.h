@@ -16,6 +16,11 @@ struct FusedDir {
   float* lse;          // MODE 0 (optional): log2-sum-exp2 of each query row's logits x log2(e),
                        //   [B][HWp] (rows HW..HWp-1 get +inf)
   const float* klse;   // MODE 1: per-KEY normaliser in the same units, [B][HWp], +inf padded
+  // Indexed operands (cn_coatt_fused_fwd_idx): q / k / v are banks [T*HW][ld] and pair b reads
+  // its query frame qi[b] and its key AND value frame kvi[b] (K and V always share the frame);
+  // NULL: frame b, the dense stack.  Outputs, lse and partial slots stay addressed by b.
+  const int* qi;
+  const int* kvi;
 };
 struct FusedArgs {
   FusedDir dir[2];

@@ -108,9 +108,13 @@ void coatt_fused_fwd_k(FusedArgs a) {
   const FusedDir d = a.dir[bd % a.ndir];
   const int HW = a.HW;
   const long long b = bd / a.ndir;
-  const bf16* Q = d.q + b * HW * d.ldq;
-  const bf16* K = d.k + b * HW * d.ldk;
-  const bf16* V = d.v + b * HW * d.ldv;
+  // operand frames: the pair's own (dense stack) or, indexed, the bank frames its maps name
+  // (workgroup-uniform scalar reads)
+  const long long fq = d.qi ? (long long)d.qi[b] : b;
+  const long long fkv = d.kvi ? (long long)d.kvi[b] : b;
+  const bf16* Q = d.q + fq * HW * d.ldq;
+  const bf16* K = d.k + fkv * HW * d.ldk;
+  const bf16* V = d.v + fkv * HW * d.ldv;
   const int q0 = rb * FBQ;
   const int qrow = q0 + w * 32 + r;
   const void* zp = (const void*)g_zero16_fused;
@@ -1122,17 +1126,19 @@ static int fused_check(const void* q, long long ldq, const void* k, long long ld
 static int fused_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
                      const void* vb, long long ld_vb, int B, int HW, int C, void* za, void* zb,
                      long long ld_z, float* lse_a, float* lse_b, void* ws, size_t ws_bytes,
-                     hipStream_t st) {
+                     hipStream_t st, const int* ia = nullptr, const int* ib = nullptr) {
   if (B <= 0 || HW <= 0) return CN_ERR_SHAPE;
+  // indexed operands exist in the 48-row and the 4-wave kernel only
+  if ((ia || ib) && coatt_variant() != 5 && coatt_variant() != 1) return CN_ERR_UNSUPPORTED;
   int rc = fused_check(vat, ld_vat, vb, ld_vb, va, ld_va, ld_z, C);
   if (rc) return rc;
   if (((uintptr_t)za & 7) || ((uintptr_t)zb & 7)) return CN_ERR_ALIGN;
   FusedArgs a = {};
   int nd = 0;
   // direction 0: Z_a = softmax_j(S) Vb  (queries i: Va_t; keys j: Vb; values Vb)
-  if (za) a.dir[nd++] = FusedDir{(const bf16*)vat, (const bf16*)vb, (const bf16*)vb, (bf16*)za, ld_vat, ld_vb, ld_vb, ld_z, lse_a, nullptr};
+  if (za) a.dir[nd++] = FusedDir{(const bf16*)vat, (const bf16*)vb, (const bf16*)vb, (bf16*)za, ld_vat, ld_vb, ld_vb, ld_z, lse_a, nullptr, ia, ib};
   // direction 1: Z_b = softmax_i(S)^T Va  (queries j: Vb; keys i: Va_t; values Va)
-  if (zb) a.dir[nd++] = FusedDir{(const bf16*)vb, (const bf16*)vat, (const bf16*)va, (bf16*)zb, ld_vb, ld_vat, ld_va, ld_z, lse_b, nullptr};
+  if (zb) a.dir[nd++] = FusedDir{(const bf16*)vb, (const bf16*)vat, (const bf16*)va, (bf16*)zb, ld_vb, ld_vat, ld_va, ld_z, lse_b, nullptr, ib, ia};
   if (nd == 0) return CN_ERR_SHAPE;
   a.HW = HW;
   a.HWp = (HW + 31) / 32 * 32;
@@ -1166,6 +1172,17 @@ extern "C" int cn_coatt_fused_fwd_ws(const void* vat, long long ld_vat, const vo
                                      void* zb, long long ld_z, void* ws, size_t ws_bytes, hipStream_t st) {
   return fused_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, C, za, zb, ld_z, nullptr, nullptr, ws,
                    ws_bytes, st);
+}
+
+// The same forward on banks [T*HW][ld] addressed through per-pair frame maps (inference over a
+// sequence: a frame encoded once serves every pair that names it).  NULL maps: the dense stack.
+extern "C" int cn_coatt_fused_fwd_idx(const void* vat, long long ld_vat, const void* va, long long ld_va,
+                                      const void* vb, long long ld_vb, const int* ia, const int* ib,
+                                      int P, int HW, int C, void* za, void* zb, long long ld_z,
+                                      void* ws, size_t ws_bytes, hipStream_t st) {
+  if (((uintptr_t)ia & 3) || ((uintptr_t)ib & 3)) return CN_ERR_ALIGN;
+  return fused_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, P, HW, C, za, zb, ld_z, nullptr, nullptr, ws,
+                   ws_bytes, st, ia, ib);
 }
 
 extern "C" int cn_coatt_flash_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,

@@ -130,9 +130,14 @@ __device__ __forceinline__ void q48_segment(const FusedArgs& a, char* lds, int* 
   const FusedDir d = a.dir[bd % a.ndir];
   const int HW = a.HW;
   const long long b = bd / a.ndir;
-  const bf16* Q = d.q + b * HW * d.ldq;
-  const bf16* K = d.k + b * HW * d.ldk;
-  const bf16* V = d.v + b * HW * d.ldv;
+  // operand frames: the pair's own (dense stack) or, indexed, the bank frames its maps name
+  // (one read of a workgroup-uniform address per segment); K and V share the frame, so K = V keeps
+  // its shortcut below
+  const long long fq = d.qi ? (long long)d.qi[b] : b;
+  const long long fkv = d.kvi ? (long long)d.kvi[b] : b;
+  const bf16* Q = d.q + fq * HW * d.ldq;
+  const bf16* K = d.k + fkv * HW * d.ldk;
+  const bf16* V = d.v + fkv * HW * d.ldv;
   const int qw0 = rb * RB + w * RW;          // this wave's first query row
 #if Q48_PROF
   unsigned long long prof_[5] = {0, 0, 0, 0, 0}, prev_ = 0;

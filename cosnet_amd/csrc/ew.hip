@@ -273,6 +273,42 @@ __global__ void gate_fwd_k(const T* __restrict__ z, long long ldz, int P, int C,
   }
 }
 
+// ---- gate + concat from a feature bank (rgbd_segmentation_RAA.py:177-186, :228-235): row
+// p HW + r of out is [z row * m | bank row iv[p] HW + r], one wave per row, one launch for both
+// halves.  A lane keeps its one 16-byte chunk of z in registers between the dot product and the
+// scaling (C <= 64 chunks: the all_channel = 256 of every call site), so every element is read
+// once and written once; the gate's arithmetic is gate_fwd_k's, in its order.
+template <class T>
+__global__ void gate_cat_idx_k(const T* __restrict__ z, long long ldz, const T* __restrict__ vbank,
+                               long long ldb, const int* __restrict__ iv, int P, int HW, int C,
+                               const float* __restrict__ g, const float* __restrict__ gb,
+                               T* __restrict__ out, long long ldo) {
+  constexpr int V = VecOf<T>::N;
+  const int lane = threadIdx.x & 63;
+  const long long row = blockIdx.x * 4ll + (threadIdx.x >> 6);
+  if (row >= (long long)P * HW) return;
+  const int p = (int)(row / HW), r = (int)(row - (long long)p * HW);
+  const long long frame = iv ? (long long)iv[p] : p;
+  const bool on = lane < C / V;
+  float f[V];
+  u32x4 vraw;
+  float acc = 0.f;
+  if (on) {
+    vraw = *(const u32x4*)(vbank + (frame * HW + r) * ldb + lane * V);   // pass-through half, raw
+    ldv(z + row * ldz + lane * V, f);
+#pragma unroll
+    for (int v = 0; v < V; ++v) acc = fmaf(f[v], g[lane * V + v], acc);
+  }
+  acc = warp_sum(acc);
+  const float m = 1.f / (1.f + expf(-(acc + (gb ? gb[0] : 0.f))));
+  if (on) {
+#pragma unroll
+    for (int v = 0; v < V; ++v) f[v] *= m;
+    stv(out + row * ldo + lane * V, f);
+    *(u32x4*)(out + row * ldo + C + lane * V) = vraw;
+  }
+}
+
 // dz = dout*m + (sum_c dout*z) * m(1-m) * g ;  dg += sum_p (.)*z ; dgb += sum_p (.)
 // one wave per row, rows grid-strided; dg / dgb reduced per block before one atomic each.
 // ---- deterministic column reductions ------------------------------------------------------
@@ -904,6 +940,27 @@ extern "C" int cn_gate_fwd(int dtype, const void* z, long long ldz, int P, int C
   return 0;
 }
 
+extern "C" int cn_gate_cat_idx(int dtype, const void* z, long long ldz, const void* vbank,
+                               long long ldv, const int* iv, int P, int HW, int C, const float* g,
+                               const float* gb, void* out, long long ldo, hipStream_t st) {
+  if (dtype != DT_BF16 && dtype != DT_F32) return CN_ERR_UNSUPPORTED;
+  if (P <= 0 || HW <= 0 || C <= 0 || ldz < C || ldv < C || ldo < 2 * C) return CN_ERR_SHAPE;
+  const int V = dtype == DT_BF16 ? 8 : 4;
+  if (C % V || ldz % V || ldv % V || ldo % V) return CN_ERR_ALIGN;
+  if (((uintptr_t)z & 15) || ((uintptr_t)vbank & 15) || ((uintptr_t)out & 15) || ((uintptr_t)iv & 3))
+    return CN_ERR_ALIGN;
+  if (C / V > 64) return CN_ERR_UNSUPPORTED;   // one chunk per lane
+  const long long rows = (long long)P * HW;
+  if (rows > 0x7fffffffll) return CN_ERR_SHAPE;
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  if (dtype == DT_BF16)
+    hipLaunchKernelGGL(gate_cat_idx_k<bf16>, grid, dim3(256), 0, st, (const bf16*)z, ldz, (const bf16*)vbank, ldv, iv, P, HW, C, g, gb, (bf16*)out, ldo);
+  else
+    hipLaunchKernelGGL(gate_cat_idx_k<float>, grid, dim3(256), 0, st, (const float*)z, ldz, (const float*)vbank, ldv, iv, P, HW, C, g, gb, (float*)out, ldo);
+  CN_CHECK_LAUNCH();
+  return 0;
+}
+
 static int rowpart_blocks(int P) { return nblocks(P, 4 * 16); }
 
 extern "C" size_t cn_colpart_workspace_floats(int P, int C) {
@@ -931,6 +988,24 @@ __global__ void mean_rows_seq_k(const float* __restrict__ x, int nrows, int C, f
 extern "C" int cn_mean_rows(const float* x, int nrows, int C, float* out, hipStream_t st) {
   if (nrows < 1 || C < 1) return CN_ERR_SHAPE;
   hipLaunchKernelGGL(mean_rows_seq_k, dim3((C + 255) / 256), dim3(256), 0, st, x, nrows, C, out);
+  CN_CHECK_LAUNCH();
+  return 0;
+}
+
+// out[g][c] = mean_rows_seq_k of rows g n .. g n + n - 1: one launch for every target of a sequence
+// (test.py:301-305 per target), the same running sum and division, so bitwise cn_mean_rows per group.
+__global__ void mean_groups_seq_k(const float* __restrict__ x, int n, int C, float* __restrict__ out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const float* xg = x + (long long)blockIdx.y * n * C;
+  float s = xg[c];
+  for (int r = 1; r < n; ++r) s += xg[(long long)r * C + c];
+  out[(long long)blockIdx.y * C + c] = s / (float)n;
+}
+
+extern "C" int cn_mean_groups(const float* x, int ngroups, int n, int C, float* out, hipStream_t st) {
+  if (ngroups < 1 || ngroups > 65535 || n < 1 || C < 1) return CN_ERR_SHAPE;
+  hipLaunchKernelGGL(mean_groups_seq_k, dim3((C + 255) / 256, ngroups), dim3(256), 0, st, x, n, C, out);
   CN_CHECK_LAUNCH();
   return 0;
 }

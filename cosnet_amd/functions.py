@@ -310,6 +310,27 @@ class CoattFn(F):
 
 
 # ==============================================================================================
+def coatt_a_materialised(vat, vb, n, hw):
+    """Z_a = softmax_j(S) V_b with S = vat vb^T, by CoattFn's materialised path (the same GEMMs
+    and softmax kernel, same arguments) without the Z_b product: the fp32 parity path of
+    RGBDSegmentation_RAA.head_a_indexed (rgbd_segmentation_RAA.py:160, :165, :170).  No autograd."""
+    c = vat.shape[1]
+    dt, dev = vat.dtype, vat.device
+    ldp = (hw + 7) // 8 * 8
+    S = torch.empty((n, hw, ldp), dtype=torch.float32, device=dev)
+    ops.gemm(vat, vb, hw, hw, c, lda=ops.ld(vat), ldb=ops.ld(vb), a_bs=hw * ops.ld(vat),
+             b_bs=hw * ops.ld(vb), out=S, ldc=ldp, c_bs=hw * ldp, batch=n, tag="affinity")   # :160
+    pc = torch.empty((n, hw, ldp), dtype=dt, device=dev)
+    pt = torch.empty((n, hw, ldp), dtype=dt, device=dev)
+    ws = torch.empty((int(nv.query("cn_coatt_workspace_floats", n, hw, ldp)),),
+                     dtype=torch.float32, device=dev)
+    nv.call("cn_coatt_softmax", nv.dtype_code(dt), S.data_ptr(), n, hw, ldp, pc.data_ptr(),
+            pt.data_ptr(), ws.data_ptr(), nv.stream())                                      # :165
+    del S, pt
+    return ops.gemm(pc, vb, hw, c, ldp, layout_b=ops.GEMM_MC, lda=ldp, ldb=ops.ld(vb),
+                    a_bs=hw * ldp, b_bs=hw * ops.ld(vb), batch=n, kb_lim=hw)                # :170
+
+
 class GateCatFn(F):
     """out = cat([z * sigmoid(z.g + gb), v], 1); mask constant (no_grad) for the b side.
     With `link` (the dict given to the CoattFn that produced z from v), v's gradient is handed

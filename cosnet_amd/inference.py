@@ -42,6 +42,137 @@ def multi_reference_x1(model, target, target_depth, searches, search_depths):
     return out
 
 
+# ---- whole-sequence inference: every frame encoded once, pairs formed by index --------------------
+#
+# test.py:287-305 forwards each target with N references drawn from the same sequence
+# (sbm_rgbd_loader.py:538-579), so over T targets the per-target path encodes (1 + N) T frames of
+# which T are distinct.  A FeatureBank holds each frame's features once; the co-attention, gate and
+# concat kernels read the frames a pair names in place (cn_coatt_fused_fwd_idx, cn_gate_cat_idx),
+# and only the a side -- all test.py uses -- is computed (RGBDSegmentation_RAA.head_a_indexed).
+
+def _as_int_list(x, what):
+    if torch.is_tensor(x):
+        x = x.tolist()
+    try:
+        return [int(v) for v in x]
+    except TypeError:
+        raise ValueError("%s: a flat list of frame indices is expected" % what)
+
+
+def plan_pairs(n_frames, targets, refs):
+    """(ia, ib) int32 CPU tensors of length Tt*N for targets [Tt] and refs [Tt][N] (lists or CPU
+    tensors of frame indices into a bank of n_frames): pair t*N + j co-attends targets[t] (a role)
+    with refs[t][j] (b role), target-major in reference order.  Self-references and repeated
+    references are legal (the reference's sampler draws both)."""
+    targets = _as_int_list(targets, "targets")
+    if torch.is_tensor(refs):
+        if refs.dim() != 2:
+            raise ValueError("refs: a [Tt][N] table is expected")
+        refs = refs.tolist()
+    refs = [_as_int_list(r, "refs[%d]" % i) for i, r in enumerate(refs)]
+    if len(refs) != len(targets):
+        raise ValueError("refs has %d rows for %d targets" % (len(refs), len(targets)))
+    n = len(refs[0]) if refs else 0
+    if n < 1:
+        raise ValueError("every target needs at least one reference (N >= 1)")
+    ia, ib = [], []
+    for t, row in zip(targets, refs):
+        if len(row) != n:
+            raise ValueError("ragged refs: rows of %d and %d references" % (n, len(row)))
+        for f in [t] + row:
+            if not 0 <= f < n_frames:
+                raise ValueError("frame index %d outside the bank of %d frames" % (f, n_frames))
+        ia += [t] * n
+        ib += row
+    return torch.tensor(ia, dtype=torch.int32), torch.tensor(ib, dtype=torch.int32)
+
+
+class FeatureBank:
+    """Per-sequence features, one entry per frame: va / da (the encoders' outputs, V of
+    rgbd_segmentation_RAA.py:143-144 / :197-203) and vat / dat (their similarity linears V W^T,
+    :158-159 / :211-212), each [T*HW][256] in the model's compute dtype with frame f at rows
+    f*HW .. f*HW + HW - 1; geo = (T, h, w) and input_size = (H, W)."""
+
+    def __init__(self, va, vat, da, dat, geo, input_size):
+        self.va, self.vat, self.da, self.dat = va, vat, da, dat
+        self.geo = tuple(geo)
+        self.input_size = tuple(input_size)
+
+    @property
+    def n_frames(self):
+        return self.geo[0]
+
+    @staticmethod
+    def _similarity(feats, linear):
+        from .functions import WCACHE
+        c = feats.shape[1]
+        wf, _ = WCACHE.get(linear.weight, feats.dtype, need_t=False)
+        return ops.gemm(feats, wf, feats.shape[0], c, c, lda=ops.ld(feats), ldb=c)
+
+    @classmethod
+    @torch.no_grad()
+    def from_features(cls, model, va, da, geo, input_size):
+        """The bank of given encoder features va / da [T*HW][C] (geo = (T, h, w))."""
+        t, h, w = geo
+        if va.shape != da.shape or va.shape[0] != t * h * w or va.dtype != model.compute_dtype:
+            raise ValueError("from_features: va / da must be [T*h*w][C] in the model's compute dtype")
+        return cls(va, cls._similarity(va, model.rgb_similarity_weights),
+                   da, cls._similarity(da, model.depth_similarity_weights), geo, input_size)
+
+    @classmethod
+    @torch.no_grad()
+    def encode(cls, model, rgbs, depths, encode_chunk=8):
+        """rgbs [T,3,H,W], depths [T,1,H,W] (fp32 NCHW on the GPU): both encoders over chunks of
+        encode_chunk frames, then the two similarity linears, once per frame."""
+        if model.training:
+            raise RuntimeError("FeatureBank.encode runs in eval mode (test.py:230)")
+        if rgbs.shape[0] != depths.shape[0] or rgbs.shape[0] < 1 or encode_chunk < 1:
+            raise ValueError("encode: T >= 1 frames of rgb and depth and encode_chunk >= 1 are expected")
+        model._set_dtype()
+        rgbs, depths = model._prep(rgbs), model._prep(depths)
+        t = rgbs.shape[0]
+        va = da = None
+        for f0 in range(0, t, encode_chunk):
+            f1 = min(t, f0 + encode_chunk)
+            v, (_, h, w) = model.encoder.features_nhwc(rgbs[f0:f1])
+            d, dgeo = model.depth_encoder.features_nhwc(depths[f0:f1])
+            if tuple(dgeo[1:]) != (h, w):
+                raise RuntimeError("RGB and depth feature maps differ: %s vs %s" % ((h, w), dgeo[1:]))
+            if va is None:
+                if f1 == t:        # one chunk: its outputs are the bank
+                    va, da = v, d
+                    break
+                va = torch.empty((t * h * w, v.shape[1]), dtype=v.dtype, device=v.device)
+                da = torch.empty_like(va)
+            ops.cast_copy(v, va[f0 * h * w:f1 * h * w])
+            ops.cast_copy(d, da[f0 * h * w:f1 * h * w])
+        return cls.from_features(model, va, da, (t, h, w), tuple(rgbs.shape[2:]))
+
+
+@torch.no_grad()
+def segment_sequence(model, rgbs, depths, refs, targets=None, encode_chunk=8, pair_chunk=10):
+    """rgbs [T,3,H,W], depths [T,1,H,W] (fp32 NCHW on the GPU), refs [Tt][N] and targets [Tt]
+    (default: every frame in order) frame indices -> [Tt,1,H,W] fp32 whose row t is
+    multi_reference_x1(model, rgbs[t], depths[t], rgbs[refs[t]], depths[refs[t]]) up to rounding:
+    every frame is encoded once and the a-side head runs over chunks of whole targets of about
+    pair_chunk pairs."""
+    t = rgbs.shape[0]
+    if targets is None:
+        targets = list(range(t))
+    ia, ib = plan_pairs(t, targets, refs)
+    nt = len(targets)
+    n = ia.shape[0] // nt
+    bank = FeatureBank.encode(model, rgbs, depths, encode_chunk)
+    hw = bank.input_size[0] * bank.input_size[1]
+    out = torch.empty((nt, 1) + bank.input_size, dtype=torch.float32, device=bank.va.device)
+    step = max(1, int(pair_chunk) // n)   # whole targets per head call
+    for t0 in range(0, nt, step):
+        t1 = min(nt, t0 + step)
+        x1 = model.head_a_indexed(bank, ia[t0 * n:t1 * n], ib[t0 * n:t1 * n])
+        ops.mean_groups(x1.view((t1 - t0) * n, hw), t1 - t0, n, out=out[t0:t1].view(t1 - t0, hw))
+    return out
+
+
 @torch.no_grad()
 def resize_linear(x, out_hw):
     """cv2.resize(..., INTER_LINEAR) of a float map (half-pixel centres, no antialias), which is

@@ -584,6 +584,55 @@ def coatt_fused(vat, va, vb, n, hw, za=None, zb=None):
     return za, zb
 
 
+def _idx(t, p):
+    if t is None:
+        return None
+    if t.dtype != torch.int32 or not t.is_cuda or t.dim() != 1 or t.shape[0] != p or not t.is_contiguous():
+        raise ValueError("frame map: a contiguous int32[%d] tensor on the GPU is expected" % p)
+    return t.data_ptr()
+
+
+def coatt_fused_idx(vat, va, vb, ia, ib, p, hw, za=None, zb=None):
+    """coatt_fused over feature banks [T*hw, C]: pair i co-attends a-role frame ia[i] (rows of vat /
+    va) with b-role frame ib[i] (rows of vb); ia / ib int32[p] on the GPU (None: frame i).  Outputs
+    stacked [p*hw, C]; either may be None (rgbd_segmentation_RAA.py:160-170 per pair of
+    test.py:287-305, every frame stored once)."""
+    c = vat.shape[1]
+    ndir = (za is not None) + (zb is not None)
+    ev = _prof_start(3 * ndir * 1.0 * p * hw * hw * c, ("coatt_fused_idx", p, hw, c),
+                     (3 * p * hw * c + ndir * p * hw * c) * vat.element_size())
+    nws = int(nv.query("cn_coatt_fused_workspace_bytes", p, hw, ndir))
+    ws = torch.empty((nws // 4,), dtype=torch.float32, device=vat.device) if nws else None
+    nv.call("cn_coatt_fused_fwd_idx", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), vb.data_ptr(),
+            ld(vb), _idx(ia, p), _idx(ib, p), p, hw, c, nv.ptr(za), nv.ptr(zb),
+            ld(za if za is not None else zb), nv.ptr(ws), nws, nv.stream())
+    _prof_end(ev)
+    return za, zb
+
+
+def gate_cat_idx(z, vbank, iv, p, hw, g, gb=None, out=None):
+    """out[i*hw + r] = [z[i*hw + r] * sigmoid(z[i*hw + r] . g + gb) | vbank[iv[i]*hw + r]]
+    (rgbd_segmentation_RAA.py:177-186, :228-235), one launch; iv int32[p] on the GPU (None: i)."""
+    c = z.shape[1]
+    if out is None:
+        out = torch.empty((p * hw, 2 * c), dtype=z.dtype, device=z.device)
+    nv.call("cn_gate_cat_idx", dtc(z), z.data_ptr(), ld(z), vbank.data_ptr(), ld(vbank), _idx(iv, p),
+            p, hw, c, g.reshape(-1).data_ptr(), nv.ptr(gb), out.data_ptr(), ld(out), nv.stream())
+    return out
+
+
+def mean_groups(x, ngroups, n, out=None):
+    """x fp32 [ngroups*n, C] contiguous -> [ngroups, C]: cn_mean_rows of every group of n rows
+    (test.py:301-305 for all targets of a sequence at once)."""
+    c = x.shape[1]
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.shape[0] != ngroups * n:
+        raise ValueError("mean_groups: a contiguous fp32 [ngroups*n, C] tensor is expected")
+    if out is None:
+        out = torch.empty((ngroups, c), dtype=torch.float32, device=x.device)
+    nv.call("cn_mean_groups", x.data_ptr(), ngroups, n, c, out.data_ptr(), nv.stream())
+    return out
+
+
 def hw_pad(hw):
     return (hw + 31) // 32 * 32
 

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import functions as fn
+from . import ops
 from .deeplab.deeplabv3_encoder import DepthEncoder_ResNetASPP, Encoder
 from .encoder_fn import encode_pair
 
@@ -245,6 +246,59 @@ class RGBDSegmentation_RAA(nn.Module):
         dz_a, dz_b = self._depth_head(da, db, geo)
         return self._decode(z_a, z_b, dz_a, dz_b, geo, input_size)
 
+    def head_a_indexed(self, bank, ia, ib):
+        """The a side of head_nhwc for pairs of frames of one feature bank
+        (cosnet_amd.inference.FeatureBank): pair p co-attends frame ia[p] (a role) with frame
+        ib[p] (b role); ia / ib int32[P] (CPU or GPU) -> x1 [P,1,H,W] fp32.  test.py:287-305 uses
+        x1 only, and x1 depends on z_a and dz_a alone (:251-266), so Z_b, the b-side gates, reduce
+        convs, BNs and classifier are not computed.  bf16: the frames are read in place by the
+        indexed kernels; fp32 (parity): stacked copies are gathered and the materialised
+        co-attention runs, a side only.  Eval mode under no_grad, no fp8."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("head_a_indexed is an inference path: eval mode under torch.no_grad()")
+        if getattr(self, "fp8", None) is not None:
+            raise RuntimeError("head_a_indexed: fp8 banks are not supported (set_fp8(False))")
+        self._set_dtype()
+        t, h, w = bank.geo
+        hw = h * w
+        dev = bank.va.device
+        ia = torch.as_tensor(ia, dtype=torch.int32).reshape(-1)
+        ib = torch.as_tensor(ib, dtype=torch.int32).reshape(-1)
+        p = ia.shape[0]
+        if p < 1 or ib.shape[0] != p:
+            raise ValueError("head_a_indexed: ia and ib must name the same number (>= 1) of pairs")
+        for m in (ia, ib):   # the kernels do not check the maps
+            if int(m.min()) < 0 or int(m.max()) >= t:
+                raise ValueError("head_a_indexed: frame index outside the bank of %d frames" % t)
+        geo = (p, h, w)
+        sides = ((bank.va, bank.vat, self.gate, self.reduce_channels_A, self.bn_A),
+                 (bank.da, bank.dat, self.depth_gate, self.depth_reduce_channels, self.depth_bn))
+        indexed = bank.va.dtype == torch.bfloat16 and ops.coatt_fused_ok(
+            torch.bfloat16, bank.va.shape[1], bank.va, bank.da)
+        if indexed:
+            ia_d, ib_d = ia.to(dev).contiguous(), ib.to(dev).contiguous()
+        else:
+            ia_h, ib_h = ia.tolist(), ib.tolist()
+        zs = []
+        for v, vt, gate, reduce, bn in sides:
+            c = v.shape[1]
+            if indexed:
+                za = torch.empty((p * hw, c), dtype=v.dtype, device=dev)
+                ops.coatt_fused_idx(vt, v, v, ia_d, ib_d, p, hw, za=za, zb=None)       # :160-170
+                cat = ops.gate_cat_idx(za, v, ia_d, p, hw, gate.weight, gate.bias)    # :177-186
+            else:
+                va_s, vat_s, vb_s = (_gather_frames(x, idx, hw) for x, idx in
+                                     ((v, ia_h), (vt, ia_h), (v, ib_h)))
+                za = fn.coatt_a_materialised(vat_s, vb_s, p, hw)
+                cat = fn.GateCatFn.apply(za, va_s, gate.weight, gate.bias, False)
+            zs.append(fn.BNFn.apply(fn.ConvFn.apply(cat, reduce.weight, None, geo, 3, 1, 1, 1),
+                                    bn.weight, bn.bias, bn))
+        z_a, dz_a = zs
+        dz_a = fn.ConvFn.apply(dz_a, self.depth_weights.weight, self.depth_weights.bias, geo, 1, 1, 0, 1)
+        la = fn.HeadFn.apply(z_a, dz_a, self.segmentation_classifier_A.weight,
+                             self.segmentation_classifier_A.bias, True)
+        return fn.UpSigFn.apply(la, geo, bank.input_size)
+
     def _rgb_head(self, va, vb, geo):
         """RGB co-attention + gate + reduce conv + BN (rgbd_segmentation_RAA.py:150-191)."""
         n, h, w = geo
@@ -290,6 +344,14 @@ class RGBDSegmentation_RAA(nn.Module):
 
 
 CoattentionModel = RGBDSegmentation_RAA  # name used by BASELINE.json's north_star
+
+
+def _gather_frames(bank, frames, hw):
+    """Stacked copy [len(frames)*hw][C] of the named frames of a bank [T*hw][C] (copy kernels)."""
+    out = torch.empty((len(frames) * hw, bank.shape[1]), dtype=bank.dtype, device=bank.device)
+    for i, f in enumerate(frames):
+        ops.cast_copy(bank[f * hw:(f + 1) * hw], out[i * hw:(i + 1) * hw])
+    return out
 
 
 class _Null:

@@ -271,6 +271,24 @@ class SBMRGBD:
         g, _ = self._prep(gt, roi, 1, None, False, off, fi.seq_name)
         return rgb, d, g[0].round().to(torch.uint8)
 
+    def _counterparts(self, idx):
+        """List indices of the counterpart frames of frame idx (:538-579): sample_range draws
+        without replacement from the frame's own sequence (the frame itself included)."""
+        st = self.sets[self.stage]
+        r = st["frame_range_of_sequences"][st["names_of_frames"][idx].seq_name]
+        if self.sample_range >= 1:
+            return self.rng.sample(list(range(r["start"], r["end"])), self.sample_range)
+        return [idx]
+
+    def reference_plan(self, idx):
+        """[target, reference_0, ...]: the list indices (into this stage's frame list) of the
+        frames __getitem__(idx) would load, drawn from the loader's RNG exactly as __getitem__
+        draws them -- in test stage one rng.sample and nothing else -- without loading pixels.
+        Whole-sequence inference plans a sequence with it and loads each distinct frame once."""
+        if idx >= len(self.sets[self.stage]["names_of_frames"]):
+            raise IndexError(idx)
+        return [idx] + self._counterparts(idx)
+
     def __getitem__(self, idx):
         st = self.sets[self.stage]
         if idx >= len(st["names_of_frames"]):
@@ -278,12 +296,7 @@ class SBMRGBD:
         fi = st["names_of_frames"][idx]
         s = {"seq_name": fi.seq_name, "frame_index": fi.id}
         s["target"], s["target_depth"], s["target_gt"] = self.load_frame(fi)
-        r = st["frame_range_of_sequences"][fi.seq_name]
-        if self.sample_range >= 1:
-            cps = self.rng.sample(list(range(r["start"], r["end"])), self.sample_range)
-        else:
-            cps = [idx]
-        for i, j in enumerate(cps):
+        for i, j in enumerate(self._counterparts(idx)):
             k = "search_%d" % i
             s[k], s[k + "_depth"], s[k + "_gt"] = self.load_frame(st["names_of_frames"][j])
         return s

@@ -310,6 +310,19 @@ int cn_coatt_f8_train_fwd(const void* vat, long long ld_vat, const void* va, lon
 int cn_coatt_fused_fwd_ws(const void* vat, long long ld_vat, const void* va, long long ld_va,
                           const void* vb, long long ld_vb, int B, int HW, int C, void* za, void* zb,
                           long long ld_z, void* ws, size_t ws_bytes, hipStream_t stream);
+/* cn_coatt_fused_fwd_ws over a feature BANK (whole-sequence inference: test.py:287-305 runs
+ * rgbd_segmentation_RAA.py:160-170 / :213-221 once per (target, reference) pair, on frames of one
+ * sequence): vat / va / vb are [T*HW][ld] with frame f at row f*HW (vb may equal va); pair p
+ * co-attends a-role frame ia[p] with b-role frame ib[p] (device int32[P], 0 <= index < T
+ * guaranteed by the caller, not checked).  A NULL map is the identity (frame p): with both NULL
+ * this is cn_coatt_fused_fwd_ws.  Outputs stay stacked, pair p at row p*HW; za or zb may be NULL.
+ * Workspace (cn_coatt_fused_workspace_bytes(P, HW, ndir)), checks, statuses and the unsplit
+ * fallback as cn_coatt_fused_fwd_ws.  Kernel variants 5 (default) and 1; CN_ERR_UNSUPPORTED with
+ * a map under a forced experimental variant 2-4. */
+int cn_coatt_fused_fwd_idx(const void* vat, long long ld_vat, const void* va, long long ld_va,
+                           const void* vb, long long ld_vb, const int* ia, const int* ib, int P,
+                           int HW, int C, void* za, void* zb, long long ld_z, void* ws,
+                           size_t ws_bytes, hipStream_t stream);
 
 /* Flash-style co-attention for TRAINING (rgbd_segmentation_RAA.py:160-170 and its autograd),
  * S never in HBM.  Forward = cn_coatt_fused_fwd plus the per-row log2-sum-exp2 of each direction
@@ -389,6 +402,21 @@ int cn_gate_bwd(int dtype, const void* z, long long ldz, const void* dout, long 
 /* Mean of N stacked fp32 maps [N][C] -> [C] (N-reference average, test.py:287-305): the fixed-
  * order sum divided by N, like the reference's `output_sum / sample_range` (test.py:305). */
 int cn_mean_rows(const float* x, int nrows, int C, float* out, hipStream_t stream);
+/* cn_mean_rows of ngroups consecutive groups of n maps in one launch: out[g] = the fixed-order
+ * sum of rows g*n .. g*n+n-1 divided by n (test.py:301-305 for every target of a sequence);
+ * bitwise cn_mean_rows per group. */
+int cn_mean_groups(const float* x, int ngroups, int n, int C, float* out, hipStream_t stream);
+/* Gate and concat with the pass-through half read from a feature bank
+ * (rgbd_segmentation_RAA.py:177-186 RGB, :228-235 depth; torch.cat of :186 / :235): for pair p
+ * and pixel r, out[p*HW+r][0:C] = z[p*HW+r] * sigmoid(z[p*HW+r].g + gb) and out[p*HW+r][C:2C] =
+ * vbank[iv[p]*HW+r][0:C] (iv device int32[P], NULL: frame p), one launch, every element read
+ * and written once.  dtypes and gate arithmetic of cn_gate_fwd (bitwise cn_gate_fwd followed by
+ * a copy of the gathered rows); 16-byte aligned bases, C and the row strides multiples of the
+ * 16-byte vector, at most 64 vectors per row (C <= 512 bf16 / 256 fp32; all_channel is 256),
+ * ldo >= 2C. */
+int cn_gate_cat_idx(int dtype, const void* z, long long ldz, const void* vbank, long long ldv,
+                    const int* iv, int P, int HW, int C, const float* g, const float* gb, void* out,
+                    long long ldo, hipStream_t stream);
 /* Fixed-order column sums of [nrows][C] fp32 (e.g. the per-channel PReLU gradient partials of
  * deeplab/deeplabv3_encoder.py:82 -> the single PReLU weight's gradient). */
 int cn_sum_rows(const float* x, int nrows, int C, float* out, hipStream_t stream);

@@ -14,6 +14,9 @@ average and the resize are HIP kernels; only the uint8 masks cross to the host. 
 load with torch.load(weights_only=True); "module." prefixes are stripped (test.py:140-161).
 `--dataset sbmrgbd` reads the SBM-RGBD tree (cosnet_amd/sbm_rgbd.py, GPU frame preparation);
 `--dataset synthetic` evaluates seeded frame pairs (cosnet_amd/data.py).
+`--feature-bank` (sbmrgbd): the references of a target are frames of its own sequence, so each
+sequence's frames are loaded and encoded ONCE and the pairs are formed by index
+(cosnet_amd.inference.segment_sequence); same log lines, order and PNGs.
 """
 import argparse
 import datetime
@@ -46,6 +49,9 @@ def get_arguments(argv=None):
                    help="bf16 (default): the MI355X throughput path, fused co-attention; fp32: the reference arithmetic")
     p.add_argument("--result-root", default=".")
     p.add_argument("--frames", type=int, default=None, help="synthetic: number of target frames")
+    p.add_argument("--feature-bank", action="store_true",
+                   help="whole-sequence inference: encode every frame of a sequence once and form the "
+                        "(target, reference) pairs by index (cosnet_amd.inference.segment_sequence)")
     return p.parse_args(argv)
 
 
@@ -77,7 +83,7 @@ def main(argv=None):
     import cosnet_amd as C
     from cosnet_amd.checkpoint import convert_state_dict, load_checkpoint
     from cosnet_amd.data import SyntheticRGBDPairs
-    from cosnet_amd.inference import multi_reference_x1, resize_linear, soft_iou
+    from cosnet_amd.inference import multi_reference_x1, resize_linear, segment_sequence, soft_iou
 
     with open(args.config) as f:
         user_config = yaml.safe_load(f)
@@ -108,6 +114,32 @@ def main(argv=None):
     model.eval()
     model.to(dev)
 
+    out_dir = None
+    if str(args.save_seg_img) not in ("False", "0", ""):
+        out_dir = os.path.join(args.result_dir, "obj_seg_imgs")
+        os.makedirs(out_dir, exist_ok=True)
+    out_hw = (args.output_WH[1], args.output_WH[0])
+    score = {"sum": 0.0, "n": 0}
+
+    def emit(x1, gt, seq, frame):
+        """Resize, quantise, score, log and save one target's mean x1 [1,1,h,w] (test.py:307-340)."""
+        gt = gt.unsqueeze(1).float()
+        if tuple(gt.shape[2:]) != out_hw:
+            gt = torch.nn.functional.interpolate(gt, size=out_hw, mode="nearest")
+        # uint8 quantisation (:317) + soft-J (evaluation.py:3-22) in one HIP kernel
+        masks, ious, _ = soft_iou(resize_linear(x1, out_hw), gt[:, 0].to(torch.uint8).to(dev))
+        mask = masks[0].cpu().numpy()                                  # [H,W] uint8
+        iou = float(ious[0].item())
+        logger.write(LOG_START + " seq: " + seq + " frame: " + frame + " IOU: " + str(iou) + LOG_END + "\n")
+        score["sum"] += iou
+        score["n"] += 1
+        if out_dir:
+            from PIL import Image
+            d = os.path.join(out_dir, seq)
+            os.makedirs(d, exist_ok=True)
+            Image.fromarray(mask).save(os.path.join(d, "%s.png" % frame))
+
+    db = None
     if args.dataset == "sbmrgbd":
         from cosnet_amd.sbm_rgbd import SBMRGBD
         if not args.data_path or not os.path.isdir(args.data_path):
@@ -115,43 +147,53 @@ def main(argv=None):
         sbm = SBMRGBD(args.data_path, args.sample_range, args.image_HW_4_model, for_training=False,
                       batch_size=args.batch_size, subset_percentage=1, subset=args.subset or None,
                       device=dev)  # test.py:271-272
-        db = [sbm.collate([sbm[j] for j in range(i, i + args.batch_size)])
-              for i in range(0, len(sbm), args.batch_size)]
+        if args.feature_bank:
+            # the plans of all targets in index order (the RNG draws of __getitem__, no pixels), then
+            # sequence by sequence (a sequence's frames are contiguous): every distinct frame loaded
+            # and encoded once, targets scored and logged in index order
+            frames = sbm.sets[sbm.stage]["names_of_frames"]
+            n = len(sbm)
+            plans = [sbm.reference_plan(i) for i in range(n)]
+            k = 0
+            while k < n:
+                k1 = k
+                while k1 < n and frames[k1].seq_name == frames[k].seq_name:
+                    k1 += 1
+                used = sorted({f for pl in plans[k:k1] for f in pl})
+                pos = {f: i for i, f in enumerate(used)}
+                loaded = [sbm.load_frame(frames[f]) for f in used]
+                x1 = segment_sequence(model, torch.stack([l[0] for l in loaded]),
+                                      torch.stack([l[1] for l in loaded]),
+                                      [[pos[f] for f in pl[1:]] for pl in plans[k:k1]],
+                                      targets=[pos[pl[0]] for pl in plans[k:k1]])
+                for i in range(k, k1):
+                    if i % args.batch_size == 0:
+                        print("%d processd" % (i // args.batch_size))
+                    emit(x1[i - k:i - k + 1], loaded[pos[i]][2][None], frames[i].seq_name, frames[i].id)
+                k = k1
+        else:
+            db = [sbm.collate([sbm[j] for j in range(i, i + args.batch_size)])
+                  for i in range(0, len(sbm), args.batch_size)]
     elif args.dataset == "synthetic":
         db = SyntheticRGBDPairs(args.frames // args.batch_size, args.image_HW_4_model, args.batch_size,
                                 sample_range=args.sample_range, seed=4321)
     else:
         raise SystemExit("dataset %r: only sbmrgbd and synthetic are provided by this build" % args.dataset)
-    out_dir = None
-    if str(args.save_seg_img) not in ("False", "0", ""):
-        out_dir = os.path.join(args.result_dir, "obj_seg_imgs")
-        os.makedirs(out_dir, exist_ok=True)
-    out_hw = (args.output_WH[1], args.output_WH[0])
-    iou_sum, iou_n = 0.0, 0
-    for index, batch in enumerate(db):
+    for index, batch in enumerate(db or ()):
         print("%d processd" % index)
         for j in range(args.batch_size):
             tgt = batch["target"][j:j + 1].to(dev)
             tdep = batch["target_depth"][j:j + 1].to(dev)
             srch = torch.cat([batch["search_%d" % i][j:j + 1] for i in range(args.sample_range)]).to(dev)
             sdep = torch.cat([batch["search_%d_depth" % i][j:j + 1] for i in range(args.sample_range)]).to(dev)
-            x1 = multi_reference_x1(model, tgt, tdep, srch, sdep)          # [1,1,h,w]
-            gt = batch["target_gt"][j:j + 1].unsqueeze(1).float()
-            if tuple(gt.shape[2:]) != out_hw:
-                gt = torch.nn.functional.interpolate(gt, size=out_hw, mode="nearest")
-            # uint8 quantisation (:317) + soft-J (evaluation.py:3-22) in one HIP kernel
-            masks, ious, _ = soft_iou(resize_linear(x1, out_hw), gt[:, 0].to(torch.uint8).to(dev))
-            mask = masks[0].cpu().numpy()                                  # [H,W] uint8
-            iou = float(ious[0].item())
-            seq, frame = batch["seq_name"][j], batch["frame_index"][j]
-            logger.write(LOG_START + " seq: " + seq + " frame: " + frame + " IOU: " + str(iou) + LOG_END + "\n")
-            iou_sum += iou
-            iou_n += 1
-            if out_dir:
-                from PIL import Image
-                d = os.path.join(out_dir, seq)
-                os.makedirs(d, exist_ok=True)
-                Image.fromarray(mask).save(os.path.join(d, "%s.png" % frame))
+            if args.feature_bank:
+                # synthetic frames belong to no sequence: a bank of the target and its own references
+                x1 = segment_sequence(model, torch.cat([tgt, srch]), torch.cat([tdep, sdep]),
+                                      [list(range(1, args.sample_range + 1))], targets=[0])
+            else:
+                x1 = multi_reference_x1(model, tgt, tdep, srch, sdep)      # [1,1,h,w]
+            emit(x1, batch["target_gt"][j:j + 1], batch["seq_name"][j], batch["frame_index"][j])
+    iou_sum, iou_n = score["sum"], score["n"]
     final = iou_sum / max(iou_n, 1)
     logger.write(LOG_START + " final IOU: " + str(final) + LOG_END + "\n")
     logger.close()
