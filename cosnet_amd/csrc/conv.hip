@@ -1,5 +1,10 @@
 // C-ABI entry points of the convolution / matrix-product family.  Each maps one reference
 // aten call onto the implicit-GEMM kernel in gemm.hip (see include/cosnet_hip.h).
+//
+// Every entry builds its GemmArgs with one of three builders -- conv_fwd_args, conv_dgrad_args,
+// conv_wgrad_args -- and then sets only what it does differently (split-K slabs, fp8 scales, a BN
+// epilogue, a group).  What an entry validates, and in which order, is part of its contract: the
+// builders take flags where the entries differ.
 #include "gemm.h"
 #include "../../include/cosnet_hip.h"
 
@@ -32,6 +37,86 @@ static int vec_of(int dtype) {
   return dtype == DT_BF16 ? 8 : (dtype == DT_FP8 || dtype == DT_FP8_E5M2) ? 16 : 4;
 }
 
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+// fp8 operands: rows of whole 16-byte chunks from 16-byte aligned bases
+static bool fp8_operands_ok(int C, long long ld, const void* a, const void* b) {
+  return !(C % 16 || ld % 16 || misaligned16(a) || misaligned16(b));
+}
+
+static int conv_out(int in, int k, int stride, int pad, int dil) {
+  return (in + 2 * pad - dil * (k - 1) - 1) / stride + 1;
+}
+
+// ---- the three problems ---------------------------------------------------------------------
+// Forward: M = output pixels, N = Cout, K = KH*KW*Cin; A = x (dense for a plain 1x1, else the
+// gather), B = w [Cout][KH][KW][Cin].
+static int conv_fwd_args(int dtype, const void* x, long long ldx, int N, int H, int W, int Cin,
+                         const void* w, int Cout, int KH, int KW, int stride, int pad, int dil,
+                         const float* bias, void* y, long long ldy, int OH, int OW, GemmArgs& a,
+                         int& la) {
+  if (Cin % vec_of(dtype) || ldx % vec_of(dtype)) return CN_ERR_ALIGN;
+  if (OH != conv_out(H, KH, stride, pad, dil)) return CN_ERR_SHAPE;
+  if (OW != conv_out(W, KW, stride, pad, dil)) return CN_ERR_SHAPE;
+  a = gemm_defaults();
+  a.M = N * OH * OW; a.N = Cout; a.K = KH * KW * Cin;
+  a.ka_lim = a.kb_lim = a.K;
+  a.A = x; a.lda = ldx;
+  a.B = w; a.ldb = a.K;
+  a.C = y; a.ldc = ldy;
+  a.bias = bias;
+  la = L_KC_CONV;
+  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) la = L_KC_DENSE;
+  else a.ga = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
+  return 0;
+}
+
+// Stride-1 input gradient: M = input pixels, N = Cin, K = KH*KW*Cout; A = dy, B = the transposed
+// weights [Cin][KH][KW][Cout]:  dX[n,h,w] = sum_{r,s} dY[n, h + pad - r*dil, w + pad - s*dil] . W[r,s].
+// Only the fp8 entry checks the output size (check_out).
+static int conv_dgrad_args(const void* dy, long long lddy, int N, int OH, int OW, int Cout,
+                           const void* wt, int Cin, int KH, int KW, int pad, int dil, void* dx,
+                           long long lddx, int H, int W, int accumulate, bool check_out,
+                           GemmArgs& a, int& la) {
+  if (check_out && (OH != conv_out(H, KH, 1, pad, dil) || OW != conv_out(W, KW, 1, pad, dil)))
+    return CN_ERR_SHAPE;
+  a = gemm_defaults();
+  a.M = N * H * W; a.N = Cin; a.K = KH * KW * Cout;
+  a.ka_lim = a.kb_lim = a.K;
+  a.A = dy; a.lda = lddy;
+  a.B = wt; a.ldb = a.K;
+  a.C = dx; a.ldc = lddx;
+  a.c_mode = accumulate ? 2 : 0;
+  la = L_KC_DENSE;
+  if (!(KH == 1 && KW == 1 && pad == 0)) {
+    la = L_KC_CONV;
+    a.ga = make_geom(N, OH, OW, Cout, H, W, KH, KW, 1, pad, pad, -dil, -dil);
+  }
+  return 0;
+}
+
+// Weight gradient: M = Cout, N = KH*KW*Cin, K = output pixels; A = dy and B = x, both k-major
+// (pixel rows), C = dW fp32 [Cout][KH][KW][Cin].  The operand pointers are the caller's (one
+// problem, or wgrad_group).  G: problems of the launch.
+static int conv_wgrad_args(int vec, int G, long long ldx, int N, int H, int W, int Cin, long long lddy,
+                           int OH, int OW, int Cout, int KH, int KW, int stride, int pad, int dil,
+                           GemmArgs& a, int& lb) {
+  if (G < 1 || G > GEMM_MAXG) return CN_ERR_SHAPE;
+  if (Cin % vec || Cout % vec) return CN_ERR_ALIGN;
+  a = gemm_defaults();
+  a.M = Cout; a.N = KH * KW * Cin; a.K = N * OH * OW;
+  a.ka_lim = a.kb_lim = a.K;
+  a.lda = lddy;
+  a.ldb = ldx;
+  a.ldc = a.N;
+  lb = L_MC_DENSE;
+  if (!(KH == 1 && KW == 1 && stride == 1 && pad == 0)) {
+    lb = L_MC_CONV;
+    a.gb = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
+  }
+  return 0;
+}
+
 // zero-fill with 16-byte vector stores (a kernel, not a memset node, inside captured graphs)
 __global__ void zero16_k(u32x4* p, long long n16) {
   const u32x4 z = {0u, 0u, 0u, 0u};
@@ -55,19 +140,11 @@ extern "C" int cn_conv_fwd(int dtype, const void* x, long long ldx, int N, int H
                            const void* w, int Cout, int KH, int KW, int stride, int pad, int dil,
                            const float* bias, void* y, long long ldy, int OH, int OW,
                            hipStream_t st) {
-  if (Cin % vec_of(dtype) || ldx % vec_of(dtype)) return CN_ERR_ALIGN;
-  if (OH != (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1) return CN_ERR_SHAPE;
-  if (OW != (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1) return CN_ERR_SHAPE;
-  GemmArgs a = gemm_defaults();
-  a.M = N * OH * OW; a.N = Cout; a.K = KH * KW * Cin;
-  a.ka_lim = a.kb_lim = a.K;
-  a.A = x; a.lda = ldx;
-  a.B = w; a.ldb = a.K;
-  a.C = y; a.ldc = ldy;
-  a.bias = bias;
-  int la = L_KC_CONV;
-  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) la = L_KC_DENSE;
-  else a.ga = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
+  GemmArgs a;
+  int la;
+  int rc = conv_fwd_args(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, bias, y,
+                         ldy, OH, OW, a, la);
+  if (rc) return rc;
   return cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, 1, st);
 }
 
@@ -129,28 +206,22 @@ extern "C" int cn_conv_fwd_ws(int dtype, const void* x, long long ldx, int N, in
                               size_t ws_floats, hipStream_t st) {
   int ns, ch;
   const int M = N * OH * OW, K = KH * KW * Cin;
-  if (!ws || ((uintptr_t)ws & 15) || ((uintptr_t)y & 15) || ldy % 8 ||
+  if (!ws || misaligned16(ws) || misaligned16(y) || ldy % 8 ||
       !fwd_split_plan(dtype, M, Cout, K, &ns, &ch) || ws_floats < (size_t)ns * M * Cout)
     return cn_conv_fwd(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, bias, y, ldy,
                        OH, OW, st);
-  if (Cin % vec_of(dtype) || ldx % vec_of(dtype)) return CN_ERR_ALIGN;
-  if (OH != (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1) return CN_ERR_SHAPE;
-  if (OW != (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1) return CN_ERR_SHAPE;
-  GemmArgs a = gemm_defaults();
-  a.M = M; a.N = Cout; a.K = K;
-  a.ka_lim = a.kb_lim = a.K;
-  a.A = x; a.lda = ldx;
-  a.B = w; a.ldb = a.K;
-  a.C = ws; a.ldc = Cout;
+  // the GEMM writes fp32 slabs [M][Cout] into ws and takes no bias: the reduce adds it
+  GemmArgs a;
+  int la;
+  int rc = conv_fwd_args(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, nullptr, ws,
+                         Cout, OH, OW, a, la);
+  if (rc) return rc;
   a.c_mode = 3;
   a.nsplit = ns;
   a.k_chunk = ch;
   a.slab = (long long)M * Cout;
   a.cfg = 20;
-  int la = L_KC_CONV;
-  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) la = L_KC_DENSE;
-  else a.ga = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
-  int rc = cn_gemm_dispatch(a, dtype, 1, la, L_KC_DENSE, 1, st);
+  rc = cn_gemm_dispatch(a, dtype, 1, la, L_KC_DENSE, 1, st);
   if (rc) return rc;
   const long long total = (long long)M * (Cout / 8);
   long long nb = (total + 255) / 256;
@@ -161,40 +232,13 @@ extern "C" int cn_conv_fwd_ws(int dtype, const void* x, long long ldx, int N, in
   return 0;
 }
 
-// ---- conv + BatchNorm epilogues ------------------------------------------------------------
-int cn_bn_tile_stats_impl(const float* ws, long long plane, int mtiles, int BM, int M, int nseg, int C,
-                          float* mean, float* invstd, float* run_mean, float* run_var, float momentum,
-                          float eps, hipStream_t st);
-int cn_bn_tile_bwd_impl(const float* ws, int mtiles, int C, float* sum_dz, float* sum_dzxh,
-                        hipStream_t st);
-
-static int conv_fwd_args(int dtype, const void* x, long long ldx, int N, int H, int W, int Cin,
-                         const void* w, int Cout, int KH, int KW, int stride, int pad, int dil,
-                         const float* bias, void* y, long long ldy, int OH, int OW, GemmArgs& a,
-                         int& la) {
-  if (Cin % vec_of(dtype) || ldx % vec_of(dtype)) return CN_ERR_ALIGN;
-  if (OH != (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1) return CN_ERR_SHAPE;
-  if (OW != (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1) return CN_ERR_SHAPE;
-  a = gemm_defaults();
-  a.M = N * OH * OW; a.N = Cout; a.K = KH * KW * Cin;
-  a.ka_lim = a.kb_lim = a.K;
-  a.A = x; a.lda = ldx;
-  a.B = w; a.ldb = a.K;
-  a.C = y; a.ldc = ldy;
-  a.bias = bias;
-  la = L_KC_CONV;
-  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) la = L_KC_DENSE;
-  else a.ga = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
-  return 0;
-}
-
 // y (bf16) = conv2d(x8, w8) * x_scale * w_scale (+ bias): fp8 e4m3 operands (cn_fp8_quant), fp32
 // accumulation on the block-scaled 16x16x128 MFMA, per-tensor dequantisation in the epilogue.
 extern "C" int cn_conv_fwd_fp8(const void* x8, long long ldx, int N, int H, int W, int Cin,
                                const void* w8, int Cout, int KH, int KW, int stride, int pad, int dil,
                                const float* bias, void* y, long long ldy, int OH, int OW,
                                const float* x_state, const float* w_state, hipStream_t st) {
-  if (Cin % 16 || ldx % 16 || ((uintptr_t)x8 & 15) || ((uintptr_t)w8 & 15)) return CN_ERR_ALIGN;
+  if (!fp8_operands_ok(Cin, ldx, x8, w8)) return CN_ERR_ALIGN;
   GemmArgs a;
   int la;
   int rc = conv_fwd_args(DT_BF16, x8, ldx, N, H, W, Cin, w8, Cout, KH, KW, stride, pad, dil, bias, y,
@@ -212,25 +256,24 @@ extern "C" int cn_conv_dgrad_fp8(const void* dy8, long long lddy, int N, int OH,
                                  const void* wt8, int Cin, int KH, int KW, int pad, int dil,
                                  void* dx, long long lddx, int H, int W, int accumulate,
                                  const float* dy_state, const float* w_state, hipStream_t st) {
-  if (Cout % 16 || lddy % 16 || ((uintptr_t)dy8 & 15) || ((uintptr_t)wt8 & 15)) return CN_ERR_ALIGN;
-  if (lddx % 8 || ((uintptr_t)dx & 15)) return CN_ERR_ALIGN;
-  if (OH != H + 2 * pad - dil * (KH - 1) || OW != W + 2 * pad - dil * (KW - 1)) return CN_ERR_SHAPE;
-  GemmArgs a = gemm_defaults();
-  a.M = N * H * W; a.N = Cin; a.K = KH * KW * Cout;
-  a.ka_lim = a.kb_lim = a.K;
-  a.A = dy8; a.lda = lddy;
-  a.B = wt8; a.ldb = a.K;
-  a.C = dx; a.ldc = lddx;
-  a.c_mode = accumulate ? 2 : 0;
+  if (!fp8_operands_ok(Cout, lddy, dy8, wt8)) return CN_ERR_ALIGN;
+  if (lddx % 8 || misaligned16(dx)) return CN_ERR_ALIGN;
+  GemmArgs a;
+  int la;
+  int rc = conv_dgrad_args(dy8, lddy, N, OH, OW, Cout, wt8, Cin, KH, KW, pad, dil, dx, lddx, H, W,
+                           accumulate, true, a, la);
+  if (rc) return rc;
   a.scale_a = dy_state;
   a.scale_b = w_state;
-  int la = L_KC_DENSE;
-  if (!(KH == 1 && KW == 1 && pad == 0)) {
-    la = L_KC_CONV;
-    a.ga = make_geom(N, OH, OW, Cout, H, W, KH, KW, 1, pad, pad, -dil, -dil);
-  }
   return cn_gemm_dispatch(a, DT_FP8_E5M2, 0, la, L_KC_DENSE, 1, st);
 }
+
+// ---- conv + BatchNorm epilogues ------------------------------------------------------------
+int cn_bn_tile_stats_impl(const float* ws, long long plane, int mtiles, int BM, int M, int nseg, int C,
+                          float* mean, float* invstd, float* run_mean, float* run_var, float momentum,
+                          float eps, hipStream_t st);
+int cn_bn_tile_bwd_impl(const float* ws, int mtiles, int C, float* sum_dz, float* sum_dzxh,
+                        hipStream_t st);
 
 static long long mtiles_of(int dtype, int M, int N, int K) {
   const int bm = cn_gemm_bm(dtype, M, N, K, -1);
@@ -239,6 +282,27 @@ static long long mtiles_of(int dtype, int M, int N, int K) {
 
 extern "C" size_t cn_conv_fwd_bn_workspace_floats(int dtype, int M, int Cout, int K) {
   return (size_t)5 * mtiles_of(dtype, M, Cout, K) * Cout;
+}
+
+// Runs a forward conv GEMM (`a` of conv_fwd_args; `dtype`: what the dispatcher is given, DT_FP8 for
+// fp8 operands) with the train-mode BatchNorm statistics of the stored output in its epilogue
+// (st_mode 1: per-M-tile partials into ws), then reduces each problem's partials to mean / invstd
+// [nseg][Cout] and updates the running statistics, segment after segment.  G problems (a.grp
+// filled by the caller) or one: ws, mean, ... are arrays of G pointers.
+static int gemm_bn_stats(GemmArgs& a, int dtype, int la, int G, int nseg, float* const* ws,
+                         float* const* mean, float* const* invstd, float* const* run_mean,
+                         float* const* run_var, float momentum, float eps, hipStream_t st) {
+  const int bm = cn_gemm_bm(dtype, a.M, a.N, a.K, -1);
+  const long long mt = (a.M + bm - 1) / bm;
+  a.st_mode = 1;
+  a.st_ws = ws[0];
+  a.st_plane = mt * a.N;
+  a.st_seg_rows = a.M / nseg;
+  int rc = cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, G, st);
+  for (int g = 0; g < G && !rc; ++g)
+    rc = cn_bn_tile_stats_impl(ws[g], a.st_plane, (int)mt, bm, a.M, nseg, a.N, mean[g], invstd[g],
+                               run_mean[g], run_var[g], momentum, eps, st);
+  return rc;
 }
 
 // y = conv2d(x, w) + bias, and the train-mode BatchNorm statistics of y computed in the GEMM
@@ -255,16 +319,8 @@ extern "C" int cn_conv_fwd_bn(int dtype, const void* x, long long ldx, int N, in
                          ldy, OH, OW, a, la);
   if (rc) return rc;
   if (nseg < 1 || a.M % nseg || !ws) return CN_ERR_SHAPE;
-  const int bm = cn_gemm_bm(dtype, a.M, a.N, a.K, -1);
-  const long long mt = (a.M + bm - 1) / bm;
-  a.st_mode = 1;
-  a.st_ws = ws;
-  a.st_plane = mt * Cout;
-  a.st_seg_rows = a.M / nseg;
-  rc = cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, 1, st);
-  if (rc) return rc;
-  return cn_bn_tile_stats_impl(ws, a.st_plane, (int)mt, bm, a.M, nseg, Cout, mean, invstd, run_mean,
-                               run_var, momentum, eps, st);
+  return gemm_bn_stats(a, dtype, la, 1, nseg, &ws, &mean, &invstd, &run_mean, &run_var, momentum, eps,
+                       st);
 }
 
 // fp8 conv (cn_conv_fwd_fp8) with the BN statistics in its GEMM epilogue (cn_conv_fwd_bn's
@@ -276,7 +332,7 @@ extern "C" int cn_conv_fwd_fp8_bn(const void* x8, long long ldx, int N, int H, i
                                   const float* x_state, const float* w_state, int nseg, float* ws,
                                   float* mean, float* invstd, float* run_mean, float* run_var,
                                   float momentum, float eps, hipStream_t st) {
-  if (Cin % 16 || ldx % 16 || ((uintptr_t)x8 & 15) || ((uintptr_t)w8 & 15)) return CN_ERR_ALIGN;
+  if (!fp8_operands_ok(Cin, ldx, x8, w8)) return CN_ERR_ALIGN;
   GemmArgs a;
   int la;
   int rc = conv_fwd_args(DT_BF16, x8, ldx, N, H, W, Cin, w8, Cout, KH, KW, stride, pad, dil, bias, y,
@@ -285,16 +341,8 @@ extern "C" int cn_conv_fwd_fp8_bn(const void* x8, long long ldx, int N, int H, i
   if (nseg < 1 || a.M % nseg || !ws) return CN_ERR_SHAPE;
   a.scale_a = x_state;
   a.scale_b = w_state;
-  const int bm = cn_gemm_bm(DT_FP8, a.M, a.N, a.K, -1);
-  const long long mt = (a.M + bm - 1) / bm;
-  a.st_mode = 1;
-  a.st_ws = ws;
-  a.st_plane = mt * Cout;
-  a.st_seg_rows = a.M / nseg;
-  rc = cn_gemm_dispatch(a, DT_FP8, 0, la, L_KC_DENSE, 1, st);
-  if (rc) return rc;
-  return cn_bn_tile_stats_impl(ws, a.st_plane, (int)mt, bm, a.M, nseg, Cout, mean, invstd, run_mean,
-                               run_var, momentum, eps, st);
+  return gemm_bn_stats(a, DT_FP8, la, 1, nseg, &ws, &mean, &invstd, &run_mean, &run_var, momentum,
+                       eps, st);
 }
 
 // G stride-1 'same' convs of one input x and one shape that differ in dilation (pad = dil), bias
@@ -318,8 +366,6 @@ extern "C" int cn_conv_fwd_bn_grouped(int dtype, const void* x, long long ldx, i
                          ldy, H, W, a, la);
   if (rc) return rc;
   if (la != L_KC_CONV || nseg < 1 || a.M % nseg) return CN_ERR_SHAPE;
-  const int bm = cn_gemm_bm(dtype, a.M, a.N, a.K, -1);
-  const long long mt = (a.M + bm - 1) / bm;
   a.ngroup = G;
   for (int g = 0; g < G; ++g) {
     if (dil[g] < 1 || !ws[g]) return CN_ERR_SHAPE;
@@ -330,18 +376,7 @@ extern "C" int cn_conv_fwd_bn_grouped(int dtype, const void* x, long long ldx, i
     a.grp.ST[g] = ws[g];
     a.grp.dil[g] = dil[g];
   }
-  a.st_mode = 1;
-  a.st_ws = ws[0];
-  a.st_plane = mt * Cout;
-  a.st_seg_rows = a.M / nseg;
-  rc = cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, G, st);
-  if (rc) return rc;
-  for (int g = 0; g < G; ++g) {
-    rc = cn_bn_tile_stats_impl(ws[g], a.st_plane, (int)mt, bm, a.M, nseg, Cout, mean[g], invstd[g],
-                               run_mean[g], run_var[g], momentum, eps, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return gemm_bn_stats(a, dtype, la, G, nseg, ws, mean, invstd, run_mean, run_var, momentum, eps, st);
 }
 
 extern "C" size_t cn_conv_dgrad_bn_workspace_floats(int dtype, int M, int Cin, int K) {
@@ -361,20 +396,11 @@ extern "C" int cn_conv_dgrad_bn(int dtype, const void* dy, long long lddy, int N
                                 hipStream_t st) {
   if (Cout % vec_of(dtype) || lddy % vec_of(dtype) || ldx % vec_of(dtype)) return CN_ERR_ALIGN;
   if (!ws || !x || !mean || !invstd) return CN_ERR_SHAPE;
-  GemmArgs a = gemm_defaults();
-  a.N = Cin; a.K = KH * KW * Cout;
-  a.ka_lim = a.kb_lim = a.K;
-  a.A = dy; a.lda = lddy;
-  a.B = wt; a.ldb = a.K;
-  a.C = dx; a.ldc = lddx;
-  a.M = N * H * W;
-  int la = L_KC_DENSE;
-  if (!(KH == 1 && KW == 1 && pad == 0)) {
-    la = L_KC_CONV;
-    a.ga = make_geom(N, OH, OW, Cout, H, W, KH, KW, 1, pad, pad, -dil, -dil);
-  }
-  const int bm = cn_gemm_bm(dtype, a.M, a.N, a.K, -1);
-  const long long mt = (a.M + bm - 1) / bm;
+  GemmArgs a;
+  int la;
+  conv_dgrad_args(dy, lddy, N, OH, OW, Cout, wt, Cin, KH, KW, pad, dil, dx, lddx, H, W, 0, false, a,
+                  la);
+  const long long mt = mtiles_of(dtype, a.M, a.N, a.K);
   a.st_mode = 2;
   a.st_ws = ws;
   a.st_plane = mt * Cin;
@@ -390,20 +416,11 @@ extern "C" int cn_conv_dgrad(int dtype, const void* dy, long long lddy, int N, i
                              int pad, int dil, void* dx, long long lddx, int H, int W,
                              int accumulate, hipStream_t st) {
   if (Cout % vec_of(dtype) || lddy % vec_of(dtype)) return CN_ERR_ALIGN;
-  GemmArgs a = gemm_defaults();
-  a.N = Cin; a.K = KH * KW * Cout;
-  a.ka_lim = a.kb_lim = a.K;
-  a.A = dy; a.lda = lddy;
-  a.B = wt; a.ldb = a.K;
-  a.C = dx; a.ldc = lddx;
-  a.c_mode = accumulate ? 2 : 0;
+  GemmArgs a;
+  int la;
   if (stride == 1) {
-    a.M = N * H * W;
-    int la = L_KC_DENSE;
-    if (!(KH == 1 && KW == 1 && pad == 0)) {
-      la = L_KC_CONV;  // dX[n,h,w] = sum_{r,s} dY[n, h + pad - r*dil, w + pad - s*dil] . W[r,s]
-      a.ga = make_geom(N, OH, OW, Cout, H, W, KH, KW, 1, pad, pad, -dil, -dil);
-    }
+    conv_dgrad_args(dy, lddy, N, OH, OW, Cout, wt, Cin, KH, KW, pad, dil, dx, lddx, H, W, accumulate,
+                    false, a, la);
     return cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, 1, st);
   }
   if (KH != 1 || KW != 1 || pad != 0) return CN_ERR_UNSUPPORTED;
@@ -412,7 +429,7 @@ extern "C" int cn_conv_dgrad(int dtype, const void* dy, long long lddy, int N, i
   // (unless accumulating into an existing gradient).
   if (!accumulate) {
     const int vec = vec_of(dtype);
-    if (lddx < Cin || lddx % vec || Cin % vec || ((uintptr_t)dx & 15)) return CN_ERR_ALIGN;
+    if (lddx < Cin || lddx % vec || Cin % vec || misaligned16(dx)) return CN_ERR_ALIGN;
     long long n16 = (long long)N * H * W * Cin / vec;
     long long nb = (n16 + 255) / 256;
     if (lddx == Cin)
@@ -422,12 +439,15 @@ extern "C" int cn_conv_dgrad(int dtype, const void* dy, long long lddy, int N, i
                          (long long)N * H * W, Cin / vec, lddx / vec);
     CN_CHECK_LAUNCH();
   }
+  // the dense 1x1 product over the output pixels, its rows scattered to the input pixels (2oy, 2ox)
+  conv_dgrad_args(dy, lddy, N, OH, OW, Cout, wt, Cin, KH, KW, pad, dil, dx, lddx, H, W, accumulate,
+                  false, a, la);
   a.M = N * OH * OW;
   a.row_map = 1;
   a.rm_div_OW = fastdiv_make(OW);
   a.rm_div_OHW = fastdiv_make(OH * OW);
   a.rm_H = H; a.rm_W = W;
-  return cn_gemm_dispatch(a, dtype, 0, L_KC_DENSE, L_KC_DENSE, 1, st);
+  return cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, 1, st);
 }
 
 
@@ -451,29 +471,17 @@ static void wgrad_plan(int dtype, int N, int OH, int OW, int Cout, int KH, int K
   int BK = 8 * vec_of(dtype);
   long long tiles;
   int target = g_wgrad_target;
-  if (dtype == DT_FP8_E5M2) {
-    // fp8 operands: 128x128 / 8 waves (the k-major fp8 reader's tile), the bf16 block target
-    *cfg = 11;
-    tiles = cn_gemm_cfg_blocks(11, M, NN) * G;
-    if (target == 512) {
-      if (tiles >= 256) target = 1024;
-      else {
-        long long s = 512 / tiles;
-        long long maxs = K / (8 * BK);
-        if (s > maxs) s = maxs;
-        if (s < 1) s = 1;
-        target = (int)(s * tiles);
-      }
-    }
-  } else if (dtype == DT_BF16) {
-    // 128x128 / 8 waves (tools/wgrad_sweep.sh); the narrow layer-1 products get tiles that
-    // do not waste half their MFMAs: 128x64 for N <= 64, 64x128 for Cout <= 64
-    *cfg = NN <= 64 ? 12 : (M <= 64 ? 17 : 11);
+  if (dtype == DT_FP8_E5M2 || dtype == DT_BF16) {
+    // 128x128 / 8 waves (tools/wgrad_sweep.sh; for fp8 operands the k-major fp8 reader's tile); the
+    // narrow bf16 layer-1 products get tiles that do not waste half their MFMAs: 128x64 for
+    // N <= 64, 64x128 for Cout <= 64
+    *cfg = dtype == DT_FP8_E5M2 ? 11 : NN <= 64 ? 12 : (M <= 64 ? 17 : 11);
     tiles = cn_gemm_cfg_blocks(*cfg, M, NN) * G;
     // split count from a per-split sweep on the step's shapes (tools/wgrad_bench.py,
     // profiles/r03_wgrad_splits.txt): up to 512 blocks = two co-resident blocks per CU, never a
     // third round (layer-3 3x3: 8 -> 14 splits 44.6 -> 37.0 us, layer-4 3x3: 2 -> 3 splits
-    // 117.7 -> 91.6 us, layer-3 1x1: 15 -> 28 splits -4 %); many tiles (ASPP) -> 2 per tile
+    // 117.7 -> 91.6 us, layer-3 1x1: 15 -> 28 splits -4 %); many tiles (ASPP) -> 2 per tile.
+    // fp8 operands take the bf16 block target.
     if (target == 512) {
       if (tiles >= 256) target = 1024;
       else {
@@ -501,6 +509,16 @@ static void wgrad_plan(int dtype, int N, int OH, int OW, int Cout, int KH, int K
   *chunk = ch;
 }
 
+// Split-K partials into fp32 slabs of M*N floats (plain stores, no atomics); a fixed-order sum
+// follows the GEMM.
+static void wgrad_split(GemmArgs& a, int cfg, int ns, int ch) {
+  a.cfg = cfg;
+  a.nsplit = ns;
+  a.k_chunk = ch;
+  a.c_mode = 3;
+  a.slab = (long long)a.M * a.N;
+}
+
 extern "C" size_t cn_conv_wgrad_workspace_floats(int dtype, int N, int OH, int OW, int Cout, int KH,
                                                  int KW, int Cin) {
   int ns, ch, cfg;
@@ -512,35 +530,41 @@ extern "C" int cn_conv_wgrad(int dtype, const void* x, long long ldx, int N, int
                              const void* dy, long long lddy, int OH, int OW, int Cout, int KH,
                              int KW, int stride, int pad, int dil, float* dw, float* ws,
                              hipStream_t st) {
-  if (Cin % vec_of(dtype) || Cout % vec_of(dtype)) return CN_ERR_ALIGN;
-  GemmArgs a = gemm_defaults();
-  a.M = Cout; a.N = KH * KW * Cin; a.K = N * OH * OW;
-  a.ka_lim = a.kb_lim = a.K;
-  a.A = dy; a.lda = lddy;
-  a.B = x; a.ldb = ldx;
-  a.ldc = a.N;
-  int lb = L_MC_DENSE;
-  if (!(KH == 1 && KW == 1 && stride == 1 && pad == 0)) {
-    lb = L_MC_CONV;
-    a.gb = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
-  }
+  GemmArgs a;
+  int lb;
+  int rc = conv_wgrad_args(vec_of(dtype), 1, ldx, N, H, W, Cin, lddy, OH, OW, Cout, KH, KW, stride, pad,
+                           dil, a, lb);
+  if (rc) return rc;
+  a.A = dy;
+  a.B = x;
   int ns, ch, cfg;
   wgrad_plan(dtype, N, OH, OW, Cout, KH, KW, Cin, &ns, &ch, &cfg);
-  a.cfg = cfg;
-  a.nsplit = ns;
-  a.k_chunk = ch;
   if (ns == 1) {  // whole K in one block: write dw directly
+    a.cfg = cfg;
+    a.k_chunk = ch;
     a.C = dw;
     return cn_gemm_dispatch(a, dtype, 1, L_MC_DENSE, lb, 1, st);
   }
   if (!ws) return CN_ERR_SHAPE;
-  // split-K partials into fp32 slabs (plain stores, no atomics), then a fixed-order sum
+  wgrad_split(a, cfg, ns, ch);
   a.C = ws;
-  a.c_mode = 3;
-  a.slab = (long long)a.M * a.N;
-  int rc = cn_gemm_dispatch(a, dtype, 1, L_MC_DENSE, lb, 1, st);
+  rc = cn_gemm_dispatch(a, dtype, 1, L_MC_DENSE, lb, 1, st);
   if (rc) return rc;
   return cn_splitk_reduce_impl(ws, ns, a.slab, a.slab, dw, 0, st);
+}
+
+// A group's operands: problem g reads dys[g] x xs[g] and writes dws[g], or, split over K, its own
+// ns slabs of ws.  The first problem's pointers also serve the loaders' range checks (every
+// problem has this shape).
+static void wgrad_group(GemmArgs& a, int G, const void* const* xs, const void* const* dys,
+                        float* const* dws, float* ws, int ns) {
+  a.ngroup = G;
+  for (int g = 0; g < G; ++g) {
+    a.grp.A[g] = dys[g];
+    a.grp.B[g] = xs[g];
+    a.grp.C[g] = ws ? ws + (long long)g * ns * a.M * a.N : dws[g];
+  }
+  a.A = dys[0]; a.B = xs[0]; a.C = a.grp.C[0];
 }
 
 // G independent weight gradients of one conv shape (the same conv of the bottlenecks of a
@@ -552,27 +576,12 @@ extern "C" int cn_conv_wgrad_grouped(int dtype, int G, const void* const* xs, lo
                                      int H, int W, int Cin, const void* const* dys, long long lddy,
                                      int OH, int OW, int Cout, int KH, int KW, int stride, int pad,
                                      int dil, float* const* dws, hipStream_t st) {
-  if (G < 1 || G > GEMM_MAXG) return CN_ERR_SHAPE;
-  if (Cin % vec_of(dtype) || Cout % vec_of(dtype)) return CN_ERR_ALIGN;
-  GemmArgs a = gemm_defaults();
-  a.M = Cout; a.N = KH * KW * Cin; a.K = N * OH * OW;
-  a.ka_lim = a.kb_lim = a.K;
-  a.lda = lddy;
-  a.ldb = ldx;
-  a.ldc = a.N;
-  int lb = L_MC_DENSE;
-  if (!(KH == 1 && KW == 1 && stride == 1 && pad == 0)) {
-    lb = L_MC_CONV;
-    a.gb = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
-  }
-  a.ngroup = G;
-  for (int g = 0; g < G; ++g) {
-    a.grp.A[g] = dys[g];
-    a.grp.B[g] = xs[g];
-    a.grp.C[g] = dws[g];
-  }
-  // the first problem's pointers for the loaders' range checks (every problem has this shape)
-  a.A = dys[0]; a.B = xs[0]; a.C = dws[0];
+  GemmArgs a;
+  int lb;
+  int rc = conv_wgrad_args(vec_of(dtype), G, ldx, N, H, W, Cin, lddy, OH, OW, Cout, KH, KW, stride, pad,
+                           dil, a, lb);
+  if (rc) return rc;
+  wgrad_group(a, G, xs, dys, dws, nullptr, 1);
   if (dtype == DT_BF16) {
     // 256x128 tiles (3-deep ring) when they give >= 160 blocks: every block runs the whole K,
     // so the larger tile's fewer bytes per FLOP pay wherever the grid still covers most CUs
@@ -613,6 +622,22 @@ __global__ __launch_bounds__(256) void splitk_reduce_grouped_k(const float* __re
 }
 }  // namespace
 
+// The split group's launch, then the one reduce launch of its slabs into the dW[g].
+static int wgrad_group_split_run(const GemmArgs& a, int dtype, int lb, int G, float* const* dws,
+                                 const float* ws, hipStream_t st) {
+  int rc = cn_gemm_dispatch(a, dtype, 1, L_MC_DENSE, lb, G, st);
+  if (rc) return rc;
+  RedOut o;
+  for (int g = 0; g < G; ++g) o.out[g] = dws[g];
+  const long long n4 = a.slab / 4;
+  long long bx = (n4 + 255) / 256;
+  if (bx > 1024) bx = 1024;
+  hipLaunchKernelGGL(splitk_reduce_grouped_k, dim3((unsigned)bx, G), dim3(256), 0, st, ws, a.nsplit,
+                     a.slab, n4, o);
+  CN_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" size_t cn_conv_wgrad_grouped_workspace_floats(int dtype, int G, int N, int OH, int OW,
                                                          int Cout, int KH, int KW, int Cin) {
   if (G < 1) return 0;
@@ -626,50 +651,22 @@ extern "C" int cn_conv_wgrad_grouped_ws(int dtype, int G, const void* const* xs,
                                         int OH, int OW, int Cout, int KH, int KW, int stride, int pad,
                                         int dil, float* const* dws, float* ws, size_t ws_floats,
                                         hipStream_t st) {
-  if (G < 1 || G > GEMM_MAXG) return CN_ERR_SHAPE;
-  if (Cin % vec_of(dtype) || Cout % vec_of(dtype)) return CN_ERR_ALIGN;
+  GemmArgs a;
+  int lb;
+  int rc = conv_wgrad_args(vec_of(dtype), G, ldx, N, H, W, Cin, lddy, OH, OW, Cout, KH, KW, stride, pad,
+                           dil, a, lb);
+  if (rc) return rc;
   int ns, ch, cfg;
   wgrad_plan(dtype, N, OH, OW, Cout, KH, KW, Cin, &ns, &ch, &cfg, G);
-  const long long slab = (long long)Cout * KH * KW * Cin;
-  if (ns <= 1 || !ws || ws_floats < (size_t)G * ns * slab || ((uintptr_t)ws & 15) || slab % 4)
+  const long long slab = (long long)a.M * a.N;
+  if (ns <= 1 || !ws || ws_floats < (size_t)G * ns * slab || misaligned16(ws) || slab % 4)
     return cn_conv_wgrad_grouped(dtype, G, xs, ldx, N, H, W, Cin, dys, lddy, OH, OW, Cout, KH, KW,
                                  stride, pad, dil, dws, st);
   for (int g = 0; g < G; ++g)
-    if ((uintptr_t)dws[g] & 15) return CN_ERR_ALIGN;
-  GemmArgs a = gemm_defaults();
-  a.M = Cout; a.N = KH * KW * Cin; a.K = N * OH * OW;
-  a.ka_lim = a.kb_lim = a.K;
-  a.lda = lddy;
-  a.ldb = ldx;
-  a.ldc = a.N;
-  int lb = L_MC_DENSE;
-  if (!(KH == 1 && KW == 1 && stride == 1 && pad == 0)) {
-    lb = L_MC_CONV;
-    a.gb = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
-  }
-  a.ngroup = G;
-  for (int g = 0; g < G; ++g) {
-    a.grp.A[g] = dys[g];
-    a.grp.B[g] = xs[g];
-    a.grp.C[g] = ws + (long long)g * ns * slab;   // problem g's slabs
-  }
-  a.A = dys[0]; a.B = xs[0]; a.C = ws;
-  a.cfg = cfg;
-  a.nsplit = ns;
-  a.k_chunk = ch;
-  a.c_mode = 3;
-  a.slab = slab;
-  int rc = cn_gemm_dispatch(a, dtype, 1, L_MC_DENSE, lb, G, st);
-  if (rc) return rc;
-  RedOut o;
-  for (int g = 0; g < G; ++g) o.out[g] = dws[g];
-  const long long n4 = slab / 4;
-  long long bx = (n4 + 255) / 256;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(splitk_reduce_grouped_k, dim3((unsigned)bx, G), dim3(256), 0, st, (const float*)ws,
-                     ns, slab, n4, o);
-  CN_CHECK_LAUNCH();
-  return 0;
+    if (misaligned16(dws[g])) return CN_ERR_ALIGN;
+  wgrad_group(a, G, xs, dys, dws, ws, ns);
+  wgrad_split(a, cfg, ns, ch);
+  return wgrad_group_split_run(a, dtype, lb, G, dws, ws, st);
 }
 
 // ---- fp8 weight gradients (BASELINE configs[4]) ------------------------------------------------
@@ -682,10 +679,7 @@ extern "C" int cn_conv_wgrad_grouped_ws(int dtype, int G, const void* const* xs,
 // (wgrad_plan), summed in split order by one reduce launch (deterministic).
 extern "C" size_t cn_conv_wgrad_fp8_workspace_floats(int G, int N, int OH, int OW, int Cout, int KH,
                                                      int KW, int Cin) {
-  if (G < 1) return 0;
-  int ns, ch, cfg;
-  wgrad_plan(DT_FP8_E5M2, N, OH, OW, Cout, KH, KW, Cin, &ns, &ch, &cfg, G);
-  return ns > 1 ? (size_t)G * ns * Cout * KH * KW * Cin : 0;
+  return cn_conv_wgrad_grouped_workspace_floats(DT_FP8_E5M2, G, N, OH, OW, Cout, KH, KW, Cin);
 }
 
 extern "C" int cn_conv_wgrad_fp8(int G, const void* const* xs8, long long ldx, int N, int H, int W,
@@ -694,58 +688,34 @@ extern "C" int cn_conv_wgrad_fp8(int G, const void* const* xs8, long long ldx, i
                                  float* const* dws, const float* const* x_states,
                                  const float* const* dy_states, float* ws, size_t ws_floats,
                                  hipStream_t st) {
-  if (G < 1 || G > GEMM_MAXG) return CN_ERR_SHAPE;
-  if (Cin % 16 || Cout % 16 || ldx % 16 || lddy % 16) return CN_ERR_ALIGN;
+  GemmArgs a;
+  int lb;
+  int rc = conv_wgrad_args(16, G, ldx, N, H, W, Cin, lddy, OH, OW, Cout, KH, KW, stride, pad, dil, a,
+                           lb);
+  if (rc) return rc;
+  if (ldx % 16 || lddy % 16) return CN_ERR_ALIGN;
+  // a null scale state is reported as an alignment error, like a misaligned operand
   for (int g = 0; g < G; ++g)
-    if (((uintptr_t)xs8[g] & 15) || ((uintptr_t)dys8[g] & 15) || ((uintptr_t)dws[g] & 15) ||
-        !x_states[g] || !dy_states[g])
+    if (misaligned16(xs8[g]) || misaligned16(dys8[g]) || misaligned16(dws[g]) || !x_states[g] ||
+        !dy_states[g])
       return CN_ERR_ALIGN;
   int ns, ch, cfg;
   wgrad_plan(DT_FP8_E5M2, N, OH, OW, Cout, KH, KW, Cin, &ns, &ch, &cfg, G);
-  const long long slab = (long long)Cout * KH * KW * Cin;
+  const long long slab = (long long)a.M * a.N;
   const bool split = ns > 1;
-  if (split && (!ws || ws_floats < (size_t)G * ns * slab || ((uintptr_t)ws & 15) || slab % 4))
+  if (split && (!ws || ws_floats < (size_t)G * ns * slab || misaligned16(ws) || slab % 4))
     return CN_ERR_SHAPE;
-  GemmArgs a = gemm_defaults();
-  a.M = Cout; a.N = KH * KW * Cin; a.K = N * OH * OW;
-  a.ka_lim = a.kb_lim = a.K;
-  a.lda = lddy;
-  a.ldb = ldx;
-  a.ldc = a.N;
-  int lb = L_MC_DENSE;
-  if (!(KH == 1 && KW == 1 && stride == 1 && pad == 0)) {
-    lb = L_MC_CONV;
-    a.gb = make_geom(N, H, W, Cin, OH, OW, KH, KW, stride, -pad, -pad, dil, dil);
-  }
-  a.ngroup = G;
+  wgrad_group(a, G, xs8, dys8, dws, split ? ws : nullptr, ns);
   for (int g = 0; g < G; ++g) {
-    a.grp.A[g] = dys8[g];
-    a.grp.B[g] = xs8[g];
-    a.grp.C[g] = split ? (void*)(ws + (long long)g * ns * slab) : (void*)dws[g];
     a.grp.SA[g] = dy_states[g];   // state[0] = dequantisation scale
     a.grp.SB[g] = x_states[g];
   }
-  a.A = dys8[0]; a.B = xs8[0]; a.C = a.grp.C[0];
   if (split) {
-    a.cfg = 11;
-    a.nsplit = ns;
-    a.k_chunk = ch;
-    a.c_mode = 3;
-    a.slab = slab;
-  } else {
-    a.cfg = 13;   // every block runs the whole K: the 3-deep ring (as the bf16 groups)
+    wgrad_split(a, cfg, ns, ch);
+    return wgrad_group_split_run(a, DT_FP8_E5M2, lb, G, dws, ws, st);
   }
-  int rc = cn_gemm_dispatch(a, DT_FP8_E5M2, 1, L_MC_DENSE, lb, G, st);
-  if (rc || !split) return rc;
-  RedOut o;
-  for (int g = 0; g < G; ++g) o.out[g] = dws[g];
-  const long long n4 = slab / 4;
-  long long bx = (n4 + 255) / 256;
-  if (bx > 1024) bx = 1024;
-  hipLaunchKernelGGL(splitk_reduce_grouped_k, dim3((unsigned)bx, G), dim3(256), 0, st, (const float*)ws,
-                     ns, slab, n4, o);
-  CN_CHECK_LAUNCH();
-  return 0;
+  a.cfg = 13;   // every block runs the whole K: the 3-deep ring (as the bf16 groups)
+  return cn_gemm_dispatch(a, DT_FP8_E5M2, 1, L_MC_DENSE, lb, G, st);
 }
 
 extern "C" int cn_splitk_reduce(const float* ws, int nsplit, long long slab, long long n, float* out,

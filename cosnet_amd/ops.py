@@ -4,6 +4,8 @@ Activations are 2-D tensors [P, C] = NHWC flattened, possibly a channel-slice vi
 wider buffer (row stride = t.stride(0)).  Every function launches HIP kernels from
 libcosnet_hip on the current torch stream; nothing here computes with torch ops.
 """
+import ctypes
+import os
 import weakref
 
 import torch
@@ -33,6 +35,28 @@ def pool_out(h, k=3, s=2, p=1):
     if (o - 1) * s >= h + p:
         o -= 1
     return o
+
+
+def _ptrs(ts):
+    """Host array of the data pointers of tensors `ts` (None: a null pointer)."""
+    return (ctypes.c_void_p * len(ts))(*[nv.ptr(t) for t in ts])
+
+
+# ---- train-mode BatchNorm bookkeeping shared by bn_stats and the conv + BN epilogues ----------
+def _check_train_rows(m, nseg, c):
+    """Each of the nseg segments of m rows needs more than one row (torch's own error text)."""
+    if m % nseg or m // nseg <= 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size "
+                         "torch.Size([%d, %d, 1, 1])" % (m // nseg, c))
+
+
+def _momentum(bn):
+    return float(bn.momentum if bn.momentum is not None else BN_MOMENTUM)
+
+
+def _count_batches(bn, nseg):
+    """The host-side count of BN batches seen: one per segment, as one reference BN call each."""
+    bn._cn_nbt = getattr(bn, "_cn_nbt", 0) + nseg
 
 
 # ---- optional per-launch timing of the implicit-GEMM kernel (bench.py roofline) -----------
@@ -201,9 +225,7 @@ def conv_fwd_bn(x, n, h, w, wf, cout, k, stride, pad, dil, bn, nseg=1, bias=None
     cin = wf.shape[1] // (k * k)
     oh, ow = out_hw(h, w, k, stride, pad, dil)
     M = n * oh * ow
-    if M % nseg or M // nseg <= 1:
-        raise ValueError("Expected more than 1 value per channel when training, got input size "
-                         "torch.Size([%d, %d, 1, 1])" % (M // nseg, cout))
+    _check_train_rows(M, nseg, cout)
     if fwd_split_floats(x, M, cout, k * k * cin):
         # split over K: the statistics come from their own pass over the reduced output
         y, oh, ow = conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=bias)
@@ -216,13 +238,12 @@ def conv_fwd_bn(x, n, h, w, wf, cout, k, stride, pad, dil, bn, nseg=1, bias=None
     es = x.element_size()
     ev = _prof_start(2.0 * M * cout * k * k * cin, ("fwd", M, cout, k * k * cin),
                      es * (n * h * w * cin + cout * k * k * cin + M * cout))
-    mom = bn.momentum if bn.momentum is not None else BN_MOMENTUM
     nv.call("cn_conv_fwd_bn", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, wf.data_ptr(), cout, k, k,
             stride, pad, dil, nv.ptr(bias), out.data_ptr(), ld(out), oh, ow, nseg, ws.data_ptr(),
             mean.data_ptr(), invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-            float(mom), float(bn.eps), nv.stream())
+            _momentum(bn), float(bn.eps), nv.stream())
     _prof_end(ev)
-    bn._cn_nbt = getattr(bn, "_cn_nbt", 0) + nseg
+    _count_batches(bn, nseg)
     return out, oh, ow, (mean, invstd)
 
 
@@ -328,13 +349,10 @@ def conv_fwd_bn_grouped(x, n, h, w, wfs, cout, k, dils, bns, nseg=1, biases=None
     """The ASPP's atrous branches as ONE grouped launch (cn_conv_fwd_bn_grouped): for each g,
     y_g = conv(x, wfs[g], dilation dils[g], padding dils[g]) (+ biases[g]) and the BN batch
     statistics of y_g from the GEMM epilogue (as conv_fwd_bn).  Returns [(y_g, (mean, invstd))]."""
-    import ctypes
     G = len(wfs)
     cin = wfs[0].shape[1] // (k * k)
     M = n * h * w
-    if M % nseg or M // nseg <= 1:
-        raise ValueError("Expected more than 1 value per channel when training, got input size "
-                         "torch.Size([%d, %d, 1, 1])" % (M // nseg, cout))
+    _check_train_rows(M, nseg, cout)
     dev = x.device
     ys = [torch.empty((M, cout), dtype=x.dtype, device=dev) for _ in range(G)]
     means = [torch.empty((nseg * cout,), dtype=torch.float32, device=dev) for _ in range(G)]
@@ -342,18 +360,16 @@ def conv_fwd_bn_grouped(x, n, h, w, wfs, cout, k, dils, bns, nseg=1, biases=None
     nws = int(nv.query("cn_conv_fwd_bn_workspace_floats", dtc(x), M, cout, k * k * cin))
     wss = [torch.empty((nws,), dtype=torch.float32, device=dev) for _ in range(G)]
     biases = biases or [None] * G
-    P = lambda ts: (ctypes.c_void_p * G)(*[t.data_ptr() if t is not None else None for t in ts])
     es = x.element_size()
     ev = _prof_start(2.0 * G * M * cout * k * k * cin, ("fwd", M, cout * G, k * k * cin),
                      es * (n * h * w * cin + G * cout * k * k * cin + G * M * cout))
-    mom = bns[0].momentum if bns[0].momentum is not None else BN_MOMENTUM
-    nv.call("cn_conv_fwd_bn_grouped", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, G, P(wfs), cout, k, k,
-            (ctypes.c_int * G)(*dils), P(biases), P(ys), cout, nseg, P(wss), P(means), P(invs),
-            P([b.running_mean for b in bns]), P([b.running_var for b in bns]), float(mom),
-            float(bns[0].eps), nv.stream())
+    nv.call("cn_conv_fwd_bn_grouped", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, G, _ptrs(wfs), cout,
+            k, k, (ctypes.c_int * G)(*dils), _ptrs(biases), _ptrs(ys), cout, nseg, _ptrs(wss),
+            _ptrs(means), _ptrs(invs), _ptrs([b.running_mean for b in bns]),
+            _ptrs([b.running_var for b in bns]), _momentum(bns[0]), float(bns[0].eps), nv.stream())
     _prof_end(ev)
     for b in bns:
-        b._cn_nbt = getattr(b, "_cn_nbt", 0) + nseg
+        _count_batches(b, nseg)
     return [(y, (m, i)) for y, m, i in zip(ys, means, invs)]
 
 
@@ -364,9 +380,7 @@ def conv_fwd_fp8_bn(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_stat
     cin = wf8.shape[1] // (k * k)
     oh, ow = out_hw(h, w, k, stride, pad, dil)
     M = n * oh * ow
-    if M % nseg or M // nseg <= 1:
-        raise ValueError("Expected more than 1 value per channel when training, got input size "
-                         "torch.Size([%d, %d, 1, 1])" % (M // nseg, cout))
+    _check_train_rows(M, nseg, cout)
     out = torch.empty((M, cout), dtype=torch.bfloat16, device=x8.device)
     mean = torch.empty((nseg * cout,), dtype=torch.float32, device=x8.device)
     invstd = torch.empty_like(mean)
@@ -374,14 +388,13 @@ def conv_fwd_fp8_bn(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_stat
     ws = torch.empty((nws,), dtype=torch.float32, device=x8.device)
     ev = _prof_start(2.0 * M * cout * k * k * cin, ("fwd8", M, cout, k * k * cin),
                      n * h * w * cin + cout * k * k * cin + 2 * M * cout)
-    mom = bn.momentum if bn.momentum is not None else BN_MOMENTUM
     nv.call("cn_conv_fwd_fp8_bn", x8.data_ptr(), ld(x8), n, h, w, cin, wf8.data_ptr(), cout, k, k,
             stride, pad, dil, nv.ptr(bias), out.data_ptr(), ld(out), oh, ow, x_state.data_ptr(),
             w_state.data_ptr(), nseg, ws.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(mom), float(bn.eps),
+            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), _momentum(bn), float(bn.eps),
             nv.stream())
     _prof_end(ev)
-    bn._cn_nbt = getattr(bn, "_cn_nbt", 0) + nseg
+    _count_batches(bn, nseg)
     return out, oh, ow, (mean, invstd)
 
 
@@ -416,22 +429,27 @@ def conv_wgrad(x, n, h, w, cin, dy, oh, ow, cout, k, stride, pad, dil, dw=None):
 GROUP_MAX = 24       # cn_conv_wgrad_grouped's problem limit (gemm.h GEMM_MAXG)
 
 
+def _group_of(jobs, ix, idy):
+    """Checks a group of weight-gradient jobs (tuples with x at index ix, dy at idy); returns
+    (size, first x, first dy)."""
+    if not 1 <= len(jobs) <= GROUP_MAX:
+        raise ValueError("1..%d problems per grouped launch" % GROUP_MAX)
+    if any(t is None for j in jobs for t in j):
+        raise ValueError("grouped weight gradients take no missing tensor")
+    x0, dy0 = jobs[0][ix], jobs[0][idy]
+    if any(ld(j[ix]) != ld(x0) or ld(j[idy]) != ld(dy0) for j in jobs):
+        raise ValueError("grouped weight gradients need equal row strides")
+    return len(jobs), x0, dy0
+
+
 def conv_wgrad_grouped(jobs, n, h, w, cin, oh, ow, cout, k, stride, pad, dil, split=False):
     """Weight gradients of G convs of ONE shape in one launch (cn_conv_wgrad_grouped): jobs =
     [(x, dy, dw)] with x [n*h*w, cin], dy [n*oh*ow, cout] sharing the row strides, dw fp32
     [cout, k*k*cin] (written).  No split-K workspace and no reduce launch.  split=True: the G
     problems also split over K (cn_conv_wgrad_grouped_ws: one GEMM launch + one reduce launch
     for the group), for shapes too small to fill the chip grouped whole."""
-    import ctypes
-    g = len(jobs)
-    if not 1 <= g <= GROUP_MAX:
-        raise ValueError("1..%d problems per grouped launch" % GROUP_MAX)
-    x0, dy0, _ = jobs[0]
-    if any(ld(x) != ld(x0) or ld(dy) != ld(dy0) for x, dy, _ in jobs):
-        raise ValueError("grouped weight gradients need equal row strides")
-    xs = (ctypes.c_void_p * g)(*[x.data_ptr() for x, _, _ in jobs])
-    dys = (ctypes.c_void_p * g)(*[dy.data_ptr() for _, dy, _ in jobs])
-    dws = (ctypes.c_void_p * g)(*[dw.data_ptr() for _, _, dw in jobs])
+    g, x0, dy0 = _group_of(jobs, 0, 1)
+    xs, dys, dws = (_ptrs(ts) for ts in zip(*jobs))
     es = x0.element_size()
     fl = 2.0 * n * oh * ow * cout * k * k * cin
     ev = _prof_start(g * fl, ("wgrad", cout, k * k * cin, n * oh * ow),
@@ -440,13 +458,11 @@ def conv_wgrad_grouped(jobs, n, h, w, cin, oh, ow, cout, k, stride, pad, dil, sp
                        cin)) if split else 0
     if nws:
         ws = torch.empty((nws,), dtype=torch.float32, device=x0.device)
-        nv.call("cn_conv_wgrad_grouped_ws", dtc(x0), g, ctypes.addressof(xs), ld(x0), n, h, w, cin,
-                ctypes.addressof(dys), ld(dy0), oh, ow, cout, k, k, stride, pad, dil,
-                ctypes.addressof(dws), ws.data_ptr(), nws, nv.stream())
+        nv.call("cn_conv_wgrad_grouped_ws", dtc(x0), g, xs, ld(x0), n, h, w, cin, dys, ld(dy0), oh, ow,
+                cout, k, k, stride, pad, dil, dws, ws.data_ptr(), nws, nv.stream())
     else:
-        nv.call("cn_conv_wgrad_grouped", dtc(x0), g, ctypes.addressof(xs), ld(x0), n, h, w, cin,
-                ctypes.addressof(dys), ld(dy0), oh, ow, cout, k, k, stride, pad, dil,
-                ctypes.addressof(dws), nv.stream())
+        nv.call("cn_conv_wgrad_grouped", dtc(x0), g, xs, ld(x0), n, h, w, cin, dys, ld(dy0), oh, ow,
+                cout, k, k, stride, pad, dil, dws, nv.stream())
     _prof_end(ev)
     return [dw for _, _, dw in jobs]
 
@@ -457,27 +473,15 @@ def conv_wgrad_fp8(jobs, n, h, w, cin, oh, ow, cout, k, stride, pad, dil):
     fp8 forward conv's input copy), dy8 e5m2 [n*oh*ow, cout] (the fp8 dgrad's output-gradient
     copy), their [4]-float scale states (element 0 = dequantisation scale) and dw fp32
     [cout, k*k*cin] (written).  Split over K into slabs + one reduce launch when small."""
-    import ctypes
-    g = len(jobs)
-    if not 1 <= g <= GROUP_MAX:
-        raise ValueError("1..%d problems per grouped launch" % GROUP_MAX)
-    x0, _, d0, _, _ = jobs[0]
-    if any(ld(x) != ld(x0) or ld(dy) != ld(d0) for x, _, dy, _, _ in jobs):
-        raise ValueError("grouped weight gradients need equal row strides")
-    arr = lambda vals: (ctypes.c_void_p * g)(*vals)
-    xs = arr([j[0].data_ptr() for j in jobs])
-    xst = arr([j[1].data_ptr() for j in jobs])
-    dys = arr([j[2].data_ptr() for j in jobs])
-    dst = arr([j[3].data_ptr() for j in jobs])
-    dws = arr([j[4].data_ptr() for j in jobs])
+    g, x0, d0 = _group_of(jobs, 0, 2)
+    xs, xst, dys, dst, dws = (_ptrs(ts) for ts in zip(*jobs))
     fl = 2.0 * n * oh * ow * cout * k * k * cin
     ev = _prof_start(g * fl, ("wgrad8", cout, k * k * cin, n * oh * ow),
                      g * ((n * h * w * cin + n * oh * ow * cout) + 4 * cout * k * k * cin))
     nws = int(nv.query("cn_conv_wgrad_fp8_workspace_floats", g, n, oh, ow, cout, k, k, cin))
     ws = torch.empty((nws,), dtype=torch.float32, device=x0.device) if nws else None
-    nv.call("cn_conv_wgrad_fp8", g, ctypes.addressof(xs), ld(x0), n, h, w, cin, ctypes.addressof(dys),
-            ld(d0), oh, ow, cout, k, k, stride, pad, dil, ctypes.addressof(dws), ctypes.addressof(xst),
-            ctypes.addressof(dst), nv.ptr(ws), nws, nv.stream())
+    nv.call("cn_conv_wgrad_fp8", g, xs, ld(x0), n, h, w, cin, dys, ld(d0), oh, ow, cout, k, k, stride,
+            pad, dil, dws, xst, dst, nv.ptr(ws), nws, nv.stream())
     _prof_end(ev)
     return [j[4] for j in jobs]
 
@@ -556,10 +560,8 @@ def gemm(a, b, m, n, k, layout_a=GEMM_KC, layout_b=GEMM_KC, lda=None, ldb=None, 
 
 
 # ---- fused co-attention (inference) ----------------------------------------------------------
-import os as _os
-
 # COSNET_COATT_FUSED=0 keeps the materialised-S path for inference too (A/B, tests)
-COATT_FUSED = _os.environ.get("COSNET_COATT_FUSED", "1") != "0"
+COATT_FUSED = os.environ.get("COSNET_COATT_FUSED", "1") != "0"
 
 
 def coatt_fused_ok(dt, c, va, vb):
@@ -752,16 +754,13 @@ def bn_stats(x, bn, training, nseg=1, count_update=True):
     mean = torch.empty((nseg * c,), dtype=torch.float32, device=x.device)
     invstd = torch.empty_like(mean)
     if training:
-        if p <= 1:
-            raise ValueError("Expected more than 1 value per channel when training, got input size "
-                             "torch.Size([%d, %d, 1, 1])" % (p, c))
+        _check_train_rows(p, 1, c)
         ws = _ws(x.dtype, p, c, x.device, nseg)
-        mom = bn.momentum if bn.momentum is not None else BN_MOMENTUM
         nv.call("cn_bn_stats", dtc(x), x.data_ptr(), ld(x), p, nseg, c, mean.data_ptr(),
-                invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(mom),
-                float(bn.eps), ws.data_ptr(), nv.stream())
+                invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+                _momentum(bn), float(bn.eps), ws.data_ptr(), nv.stream())
         if count_update:
-            bn._cn_nbt = getattr(bn, "_cn_nbt", 0) + nseg
+            _count_batches(bn, nseg)
     else:
         nv.call("cn_bn_eval_params", bn.running_mean.data_ptr(), bn.running_var.data_ptr(), c,
                 float(bn.eps), mean.data_ptr(), invstd.data_ptr(), nv.stream())
