@@ -293,6 +293,9 @@ struct F8Dir {
   const unsigned char* vt8; const unsigned char* vts;  // [B][nt][256][64], [B][nt][512]
   bf16* o; long long ldo;
   float* lse;                                          // optional [B][HWp32] log2-sum-exp2
+  // optional frame maps (cn_coatt_f8_fwd_idx): batch entry b reads its Q image at entry qmap[b]
+  // and its K / V^T images at entry kmap[b]; NULL = b.  The output stays at b.
+  const int* qmap; const int* kmap;
 };
 struct F8Args {
   F8Dir dir[2];
@@ -315,12 +318,15 @@ void coatt_f8_fwd_k(F8Args a) {
   const long long b = bd / a.ndir;
   const int HW = a.HW;
   const int q0 = rb * QB;
-  const unsigned char* Q8 = d.q8 + (b * a.HWp + q0) * D;
-  const unsigned char* Qs = d.qs + (b * a.HWp + q0) * 8;
-  const unsigned char* K8 = d.k8 + b * a.HWp * D;
-  const unsigned char* Ks = d.ks + b * a.HWp * 8;
-  const unsigned char* VT8 = d.vt8 + b * a.nt * VBYTES;
-  const unsigned char* VTs = d.vts + b * a.nt * 512;
+  // b is workgroup-uniform: one scalar load per map
+  const long long bq = d.qmap ? d.qmap[b] : b;
+  const long long bk = d.kmap ? d.kmap[b] : b;
+  const unsigned char* Q8 = d.q8 + (bq * a.HWp + q0) * D;
+  const unsigned char* Qs = d.qs + (bq * a.HWp + q0) * 8;
+  const unsigned char* K8 = d.k8 + bk * a.HWp * D;
+  const unsigned char* Ks = d.ks + bk * a.HWp * 8;
+  const unsigned char* VT8 = d.vt8 + bk * a.nt * VBYTES;
+  const unsigned char* VTs = d.vts + bk * a.nt * 512;
   char* qlds = lds;
   char* qslds = lds + QBYTES;
   char* ring = lds + QBYTES + 1024;
@@ -601,6 +607,92 @@ static int f8_fwd(const void* vat, long long ld_vat, const void* va, long long l
   a.HW = HW; a.HWp = HWp; a.HWp32 = (HW + 31) / 32 * 32; a.nt = nt; a.ndir = 2;
   a.nrb = (HW + QB - 1) / QB;
   a.nitems = a.nrb * B * 2;
+  hipLaunchKernelGGL(coatt_f8_fwd_k, dim3((a.nitems + 7) & ~7), dim3(256), 0, st, a);
+  CN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- MX image bank (whole-sequence inference) ---------------------------------------------------
+// One modality's images for T frames, each written once per sequence: the row image of vat (the
+// Q role), the row image of va (K) and the V^T tile image of va (V), every frame's bytes being
+// what the inference prepass above writes for it (an MX image is a function of its own frame's
+// rows only).  Sub-buffers are 256-byte aligned.
+namespace {
+struct F8Bank {
+  unsigned char* q8; unsigned char* k8; unsigned char* qs; unsigned char* ks;
+  unsigned char* vt8; unsigned char* vts;
+  size_t bytes;
+};
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline F8Bank f8_bank_layout(void* img, int T, int HW) {
+  const size_t rows = (size_t)T * hwq128(HW);
+  const size_t tiles = (size_t)T * (hwp64(HW) / KT);
+  F8Bank k;
+  size_t o = 0;
+  unsigned char* p = (unsigned char*)img;
+  k.q8 = p + o;  o = al256(o + rows * D);
+  k.k8 = p + o;  o = al256(o + rows * D);
+  k.qs = p + o;  o = al256(o + rows * 8);
+  k.ks = p + o;  o = al256(o + rows * 8);
+  k.vt8 = p + o; o = al256(o + tiles * VBYTES);
+  k.vts = p + o; o = al256(o + tiles * 512);
+  k.bytes = o;
+  return k;
+}
+}  // namespace
+
+extern "C" size_t cn_coatt_f8_bank_bytes(int T, int HW) {
+  if (T <= 0 || HW <= 0) return 0;
+  return f8_bank_layout(nullptr, T, HW).bytes;
+}
+
+extern "C" int cn_coatt_f8_bank_build(const void* vat, long long ld_vat, const void* va, long long ld_va,
+                                      int T, int HW, int C, void* img, size_t img_bytes,
+                                      hipStream_t st) {
+  if (T <= 0 || HW <= 0 || C != D || !vat || !va) return CN_ERR_SHAPE;
+  if (ld_vat % 8 || ld_va % 8 || ld_vat < C || ld_va < C) return CN_ERR_ALIGN;
+  if (((uintptr_t)vat & 15) || ((uintptr_t)va & 15)) return CN_ERR_ALIGN;
+  if (!img || ((uintptr_t)img & 255) || img_bytes < cn_coatt_f8_bank_bytes(T, HW)) return CN_ERR_SHAPE;
+  const int HWp = hwq128(HW), nt = hwp64(HW) / KT;
+  const long long nr = (long long)T * HWp * 8, nv = (long long)T * nt * 2 * D;
+  if ((nr + 255) / 256 > 0x7fffffffll || (nv + 255) / 256 > 0x7fffffffll) return CN_ERR_SHAPE;
+  const F8Bank k = f8_bank_layout(img, T, HW);
+  const dim3 gr((unsigned)((nr + 255) / 256)), gv((unsigned)((nv + 255) / 256));
+  hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vat, ld_vat, T, HW, HWp, k.q8, k.qs);
+  CN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)va, ld_va, T, HW, HWp, k.k8, k.ks);
+  CN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)va, ld_va, T, HW, nt, k.vt8, k.vts);
+  CN_CHECK_LAUNCH();
+  return 0;
+}
+
+// Z_a of P pairs over one or two image banks (RGB and depth share T, HW and the maps): the
+// modalities are dir[0] and dir[1] of one launch, the item order being that of the dense entry
+// (row block fastest, then modality, then pair).
+extern "C" int cn_coatt_f8_fwd_idx(const void* img0, const void* img1, int T, const int* ia,
+                                   const int* ib, int P, int HW, int C, void* za0, void* za1,
+                                   long long ld_z, hipStream_t st) {
+  if (T <= 0 || P <= 0 || HW <= 0 || C != D || !img0 || !za0) return CN_ERR_SHAPE;
+  if ((img1 == nullptr) != (za1 == nullptr)) return CN_ERR_SHAPE;
+  if ((!ia || !ib) && P > T) return CN_ERR_SHAPE;
+  if (ld_z % 4 || ld_z < C) return CN_ERR_ALIGN;
+  if (((uintptr_t)img0 & 255) || ((uintptr_t)img1 & 255) || ((uintptr_t)za0 & 7) || ((uintptr_t)za1 & 7))
+    return CN_ERR_ALIGN;
+  const int ndir = img1 ? 2 : 1;
+  const int nrb = (HW + QB - 1) / QB;
+  if ((long long)nrb * P * ndir > 0x7ffffff0ll) return CN_ERR_SHAPE;
+  F8Args a = {};
+  const void* imgs[2] = {img0, img1};
+  void* zs[2] = {za0, za1};
+  for (int m = 0; m < ndir; ++m) {
+    const F8Bank k = f8_bank_layout(const_cast<void*>(imgs[m]), T, HW);
+    // queries Va_t[ia], keys and values Va[ib]
+    a.dir[m] = F8Dir{k.q8, k.qs, k.k8, k.ks, k.vt8, k.vts, (bf16*)zs[m], ld_z, nullptr, ia, ib};
+  }
+  a.HW = HW; a.HWp = hwq128(HW); a.HWp32 = (HW + 31) / 32 * 32; a.nt = hwp64(HW) / KT; a.ndir = ndir;
+  a.nrb = nrb;
+  a.nitems = nrb * P * ndir;
   hipLaunchKernelGGL(coatt_f8_fwd_k, dim3((a.nitems + 7) & ~7), dim3(256), 0, st, a);
   CN_CHECK_LAUNCH();
   return 0;

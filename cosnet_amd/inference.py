@@ -91,12 +91,18 @@ class FeatureBank:
     """Per-sequence features, one entry per frame: va / da (the encoders' outputs, V of
     rgbd_segmentation_RAA.py:143-144 / :197-203) and vat / dat (their similarity linears V W^T,
     :158-159 / :211-212), each [T*HW][256] in the model's compute dtype with frame f at rows
-    f*HW .. f*HW + HW - 1; geo = (T, h, w) and input_size = (H, W)."""
+    f*HW .. f*HW + HW - 1; geo = (T, h, w) and input_size = (H, W).  coatt = "mxfp8" adds mx / dmx,
+    the MX-fp8 images of (vat, va) / (dat, da) (ops.coatt_f8_bank: each frame quantised once, about
+    2.9 MB per frame and modality at 473 x 473), and head_a_indexed then runs the fp8 co-attention
+    over them; the default "bf16" leaves both None."""
 
-    def __init__(self, va, vat, da, dat, geo, input_size):
+    COATT = ("bf16", "mxfp8")
+
+    def __init__(self, va, vat, da, dat, geo, input_size, mx=None, dmx=None):
         self.va, self.vat, self.da, self.dat = va, vat, da, dat
         self.geo = tuple(geo)
         self.input_size = tuple(input_size)
+        self.mx, self.dmx = mx, dmx
 
     @property
     def n_frames(self):
@@ -111,21 +117,35 @@ class FeatureBank:
 
     @classmethod
     @torch.no_grad()
-    def from_features(cls, model, va, da, geo, input_size):
+    def from_features(cls, model, va, da, geo, input_size, coatt="bf16"):
         """The bank of given encoder features va / da [T*HW][C] (geo = (T, h, w))."""
         t, h, w = geo
+        if coatt not in cls.COATT:
+            raise ValueError("coatt: one of %s is expected, not %r" % (cls.COATT, coatt))
         if va.shape != da.shape or va.shape[0] != t * h * w or va.dtype != model.compute_dtype:
             raise ValueError("from_features: va / da must be [T*h*w][C] in the model's compute dtype")
-        return cls(va, cls._similarity(va, model.rgb_similarity_weights),
-                   da, cls._similarity(da, model.depth_similarity_weights), geo, input_size)
+        if coatt == "mxfp8" and (va.dtype != torch.bfloat16 or va.shape[1] != 256):
+            raise ValueError("coatt='mxfp8' needs the bf16 compute dtype and 256 feature channels")
+        vat = cls._similarity(va, model.rgb_similarity_weights)
+        dat = cls._similarity(da, model.depth_similarity_weights)
+        mx = dmx = None
+        if coatt == "mxfp8":
+            mx = ops.coatt_f8_bank(vat, va, t, h * w)
+            dmx = ops.coatt_f8_bank(dat, da, t, h * w)
+        return cls(va, vat, da, dat, geo, input_size, mx, dmx)
 
     @classmethod
     @torch.no_grad()
-    def encode(cls, model, rgbs, depths, encode_chunk=8):
+    def encode(cls, model, rgbs, depths, encode_chunk=8, coatt="bf16"):
         """rgbs [T,3,H,W], depths [T,1,H,W] (fp32 NCHW on the GPU): both encoders over chunks of
-        encode_chunk frames, then the two similarity linears, once per frame."""
+        encode_chunk frames, then the two similarity linears (and, coatt = "mxfp8", the MX images),
+        once per frame."""
         if model.training:
             raise RuntimeError("FeatureBank.encode runs in eval mode (test.py:230)")
+        if coatt not in cls.COATT:
+            raise ValueError("coatt: one of %s is expected, not %r" % (cls.COATT, coatt))
+        if coatt == "mxfp8" and model.compute_dtype != torch.bfloat16:   # before any encoder pass
+            raise ValueError("coatt='mxfp8' needs the bf16 compute dtype")
         if rgbs.shape[0] != depths.shape[0] or rgbs.shape[0] < 1 or encode_chunk < 1:
             raise ValueError("encode: T >= 1 frames of rgb and depth and encode_chunk >= 1 are expected")
         model._set_dtype()
@@ -146,23 +166,25 @@ class FeatureBank:
                 da = torch.empty_like(va)
             ops.cast_copy(v, va[f0 * h * w:f1 * h * w])
             ops.cast_copy(d, da[f0 * h * w:f1 * h * w])
-        return cls.from_features(model, va, da, (t, h, w), tuple(rgbs.shape[2:]))
+        return cls.from_features(model, va, da, (t, h, w), tuple(rgbs.shape[2:]), coatt)
 
 
 @torch.no_grad()
-def segment_sequence(model, rgbs, depths, refs, targets=None, encode_chunk=8, pair_chunk=10):
+def segment_sequence(model, rgbs, depths, refs, targets=None, encode_chunk=8, pair_chunk=10,
+                     coatt="bf16"):
     """rgbs [T,3,H,W], depths [T,1,H,W] (fp32 NCHW on the GPU), refs [Tt][N] and targets [Tt]
     (default: every frame in order) frame indices -> [Tt,1,H,W] fp32 whose row t is
     multi_reference_x1(model, rgbs[t], depths[t], rgbs[refs[t]], depths[refs[t]]) up to rounding:
     every frame is encoded once and the a-side head runs over chunks of whole targets of about
-    pair_chunk pairs."""
+    pair_chunk pairs.  coatt = "mxfp8" (bf16 models): the co-attention runs on MX-fp8 images of
+    the bank (FeatureBank); "bf16" (default): the bf16 indexed kernel."""
     t = rgbs.shape[0]
     if targets is None:
         targets = list(range(t))
     ia, ib = plan_pairs(t, targets, refs)
     nt = len(targets)
     n = ia.shape[0] // nt
-    bank = FeatureBank.encode(model, rgbs, depths, encode_chunk)
+    bank = FeatureBank.encode(model, rgbs, depths, encode_chunk, coatt)
     hw = bank.input_size[0] * bank.input_size[1]
     out = torch.empty((nt, 1) + bank.input_size, dtype=torch.float32, device=bank.va.device)
     step = max(1, int(pair_chunk) // n)   # whole targets per head call

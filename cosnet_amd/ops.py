@@ -655,6 +655,48 @@ def coatt_f8(vat, va, vb, n, hw, za, zb, lse_a=None, lse_b=None):
     return za, zb
 
 
+def coatt_f8_bank(vat, va, t, hw):
+    """The MX-fp8 images of one modality's feature bank (vat = va W^T and va, [t*hw, 256] bf16):
+    per frame the row images of vat (Q role) and va (K) and the V^T tile image of va (V) that
+    coatt_f8's prepass writes, built once per sequence (cn_coatt_f8_bank_build) -> uint8 tensor."""
+    c = vat.shape[1]
+    for x in (vat, va):   # the kernels read t*hw rows of c bf16 values through raw pointers
+        if x.dtype != torch.bfloat16 or not x.is_cuda or x.dim() != 2 or x.shape != vat.shape \
+                or t < 1 or hw < 1 or x.shape[0] < t * hw or x.stride(1) != 1:
+            raise ValueError("coatt_f8_bank: vat / va must be bf16 [>= %d, C] tensors on the GPU" % (t * hw))
+    nb = int(nv.query("cn_coatt_f8_bank_bytes", t, hw))
+    img = torch.empty((nb,), dtype=torch.uint8, device=vat.device)
+    ev = _prof_start(0.0, ("coatt_f8_bank_build", t, hw, c), 2 * t * hw * c * vat.element_size() + nb)
+    nv.call("cn_coatt_f8_bank_build", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), t, hw, c,
+            img.data_ptr(), nb, nv.stream())
+    _prof_end(ev)
+    return img
+
+
+def coatt_f8_idx(img, img2, t, ia, ib, p, hw, za, za2=None):
+    """Z_a of p pairs with MX-fp8 operands over image banks of t frames (coatt_f8_bank): pair i
+    reads its queries at frame ia[i] and its keys / values at frame ib[i]; ia / ib int32[p] on the
+    GPU (None: frame i).  img2 / za2 (both or neither): a second modality with the same maps, run
+    in the same launch (cn_coatt_f8_fwd_idx).  Outputs stacked [p*hw, 256] bf16."""
+    c = za.shape[1]
+    if (img2 is None) != (za2 is None):
+        raise ValueError("coatt_f8_idx: img2 and za2 go together")
+    nmod = 1 if img2 is None else 2
+    if za2 is not None and (ld(za2) != ld(za) or za2.shape[1] != c):
+        raise ValueError("coatt_f8_idx: za and za2 must share their shape and row stride")
+    nb = int(nv.query("cn_coatt_f8_bank_bytes", t, hw))
+    for im in (img, img2)[:nmod]:
+        if im.dtype != torch.uint8 or not im.is_cuda or not im.is_contiguous() or im.numel() < nb:
+            raise ValueError("coatt_f8_idx: an image bank of coatt_f8_bank(., ., %d, %d) is expected" % (t, hw))
+    # a side only: 2 products of 2 P HW^2 C per modality; operands are one byte per value
+    ev = _prof_start(nmod * 2 * 2.0 * p * hw * hw * c, ("coatt_f8_fwd_idx", p, hw, c),
+                     nmod * (3 * p * hw * c + p * hw * c * za.element_size()))
+    nv.call("cn_coatt_f8_fwd_idx", img.data_ptr(), nv.ptr(img2), t, _idx(ia, p), _idx(ib, p), p, hw, c,
+            za.data_ptr(), nv.ptr(za2), ld(za), nv.stream())
+    _prof_end(ev)
+    return za, za2
+
+
 def coatt_f8_train(vat, va, vb, n, hw, za, zb, lse_a, lse_b):
     """Training forward of both directions with MX-fp8 operands (configs[4]): Z_a, Z_b, the
     per-row log2-sum-exp2 normalisers, and the decoded operands (vat_q, va_q, vb_q) -- bf16,

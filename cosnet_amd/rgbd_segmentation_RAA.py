@@ -253,7 +253,11 @@ class RGBDSegmentation_RAA(nn.Module):
         x1 only, and x1 depends on z_a and dz_a alone (:251-266), so Z_b, the b-side gates, reduce
         convs, BNs and classifier are not computed.  bf16: the frames are read in place by the
         indexed kernels; fp32 (parity): stacked copies are gathered and the materialised
-        co-attention runs, a side only.  Eval mode under no_grad, no fp8."""
+        co-attention runs, a side only.  A bank built with coatt="mxfp8" (bank.mx / bank.dmx: the
+        MX-fp8 images of its bf16 features) runs the fp8 co-attention of both modalities in one
+        launch (ops.coatt_f8_idx); gate, reduce conv, BN and classifier are unchanged.  Eval mode
+        under no_grad; the model's own fp8 mode (set_fp8: fp8 encoder convs with delayed scaling,
+        whose features depend on the order of calls) stays refused."""
         if self.training or torch.is_grad_enabled():
             raise RuntimeError("head_a_indexed is an inference path: eval mode under torch.no_grad()")
         if getattr(self, "fp8", None) is not None:
@@ -275,14 +279,22 @@ class RGBDSegmentation_RAA(nn.Module):
                  (bank.da, bank.dat, self.depth_gate, self.depth_reduce_channels, self.depth_bn))
         indexed = bank.va.dtype == torch.bfloat16 and ops.coatt_fused_ok(
             torch.bfloat16, bank.va.shape[1], bank.va, bank.da)
-        if indexed:
+        mx = bank.mx   # MX-fp8 images (bf16 features, C = 256 by construction)
+        if (mx is None) != (bank.dmx is None):
+            raise ValueError("head_a_indexed: an MX-fp8 bank holds the images of both modalities (mx and dmx)")
+        if indexed or mx is not None:
             ia_d, ib_d = ia.to(dev).contiguous(), ib.to(dev).contiguous()
         else:
             ia_h, ib_h = ia.tolist(), ib.tolist()
+        if mx is not None:   # both modalities' Z_a in one launch
+            zas = [torch.empty((p * hw, bank.va.shape[1]), dtype=torch.bfloat16, device=dev) for _ in sides]
+            ops.coatt_f8_idx(mx, bank.dmx, t, ia_d, ib_d, p, hw, zas[0], zas[1])       # :160-170, :213-221
         zs = []
-        for v, vt, gate, reduce, bn in sides:
+        for k, (v, vt, gate, reduce, bn) in enumerate(sides):
             c = v.shape[1]
-            if indexed:
+            if mx is not None:
+                cat = ops.gate_cat_idx(zas[k], v, ia_d, p, hw, gate.weight, gate.bias)  # :177-186
+            elif indexed:
                 za = torch.empty((p * hw, c), dtype=v.dtype, device=dev)
                 ops.coatt_fused_idx(vt, v, v, ia_d, ib_d, p, hw, za=za, zb=None)       # :160-170
                 cat = ops.gate_cat_idx(za, v, ia_d, p, hw, gate.weight, gate.bias)    # :177-186

@@ -307,6 +307,27 @@ int cn_coatt_f8_train_fwd(const void* vat, long long ld_vat, const void* va, lon
                           const void* vb, long long ld_vb, int B, int HW, int C, void* za, void* zb,
                           long long ld_z, float* lse_a, float* lse_b, void* vat_q, void* va_q,
                           void* vb_q, long long ld_q, void* ws, size_t ws_bytes, hipStream_t stream);
+/* MX-fp8 co-attention over a feature BANK (whole-sequence inference, test.py:287-305 running
+ * rgbd_segmentation_RAA.py:160-170 / :213-221 per (target, reference) pair of one sequence).
+ * An MX image is a function of its own frame's rows only, so every frame is quantised once:
+ * cn_coatt_f8_bank_build writes, for the T frames of one modality (vat = Va W^T and va, both
+ * [T*HW][ld] bf16, 16-byte aligned, ld % 8 == 0), the row image and exponents of vat (the Q
+ * role), the row image and exponents of va (K) and the V^T tile image and exponents of va (V)
+ * into img (256-byte aligned, img_bytes >= cn_coatt_f8_bank_bytes(T, HW); sub-buffers 256-byte
+ * aligned, rows padded to ceil128(HW), keys to ceil64(HW), padding zero).  Per frame the bytes
+ * are those of cn_coatt_f8_fwd's prepass.  C == 256.
+ * cn_coatt_f8_fwd_idx: Z_a only (softmax_j(S) V of the b-role frame) for P pairs; pair p reads
+ * its Q image at frame ia[p] and its K / V^T images at frame ib[p] (device int32[P], 0 <= index
+ * < T guaranteed by the caller, not checked; NULL: frame p, then P <= T).  img1 / za1: the second
+ * modality's bank (same T, HW and maps) and output, both NULL or both given; the two modalities
+ * run in one launch.  Outputs stacked, pair p at row p*HW, [P*HW][ld_z] bf16, 8-byte aligned,
+ * ld_z % 4 == 0; bitwise cn_coatt_f8_fwd's za on the gathered frames.  No log-sum-exp output. */
+size_t cn_coatt_f8_bank_bytes(int T, int HW);
+int cn_coatt_f8_bank_build(const void* vat, long long ld_vat, const void* va, long long ld_va, int T,
+                           int HW, int C, void* img, size_t img_bytes, hipStream_t stream);
+int cn_coatt_f8_fwd_idx(const void* img0, const void* img1, int T, const int* ia, const int* ib,
+                        int P, int HW, int C, void* za0, void* za1, long long ld_z,
+                        hipStream_t stream);
 int cn_coatt_fused_fwd_ws(const void* vat, long long ld_vat, const void* va, long long ld_va,
                           const void* vb, long long ld_vb, int B, int HW, int C, void* za, void* zb,
                           long long ld_z, void* ws, size_t ws_bytes, hipStream_t stream);

@@ -16,7 +16,8 @@ load with torch.load(weights_only=True); "module." prefixes are stripped (test.p
 `--dataset synthetic` evaluates seeded frame pairs (cosnet_amd/data.py).
 `--feature-bank` (sbmrgbd): the references of a target are frames of its own sequence, so each
 sequence's frames are loaded and encoded ONCE and the pairs are formed by index
-(cosnet_amd.inference.segment_sequence); same log lines, order and PNGs.
+(cosnet_amd.inference.segment_sequence); same log lines, order and PNGs.  With it,
+`--coatt mxfp8` (bf16 only) runs the bank's co-attention on MX-fp8 images of the features.
 """
 import argparse
 import datetime
@@ -52,7 +53,15 @@ def get_arguments(argv=None):
     p.add_argument("--feature-bank", action="store_true",
                    help="whole-sequence inference: encode every frame of a sequence once and form the "
                         "(target, reference) pairs by index (cosnet_amd.inference.segment_sequence)")
-    return p.parse_args(argv)
+    p.add_argument("--coatt", default="bf16", choices=["bf16", "mxfp8"],
+                   help="--feature-bank: the bank's co-attention.  bf16 (default): the bf16 indexed kernel; "
+                        "mxfp8: MX-fp8 images of the bf16 features, each frame quantised once per sequence")
+    args = p.parse_args(argv)
+    if args.coatt == "mxfp8" and not args.feature_bank:
+        p.error("--coatt mxfp8 needs --feature-bank")
+    if args.coatt == "mxfp8" and args.dtype != "bf16":
+        p.error("--coatt mxfp8 needs --dtype bf16")
+    return args
 
 
 def config(args, user_config):
@@ -165,7 +174,7 @@ def main(argv=None):
                 x1 = segment_sequence(model, torch.stack([l[0] for l in loaded]),
                                       torch.stack([l[1] for l in loaded]),
                                       [[pos[f] for f in pl[1:]] for pl in plans[k:k1]],
-                                      targets=[pos[pl[0]] for pl in plans[k:k1]])
+                                      targets=[pos[pl[0]] for pl in plans[k:k1]], coatt=args.coatt)
                 for i in range(k, k1):
                     if i % args.batch_size == 0:
                         print("%d processd" % (i // args.batch_size))
@@ -189,7 +198,8 @@ def main(argv=None):
             if args.feature_bank:
                 # synthetic frames belong to no sequence: a bank of the target and its own references
                 x1 = segment_sequence(model, torch.cat([tgt, srch]), torch.cat([tdep, sdep]),
-                                      [list(range(1, args.sample_range + 1))], targets=[0])
+                                      [list(range(1, args.sample_range + 1))], targets=[0],
+                                      coatt=args.coatt)
             else:
                 x1 = multi_reference_x1(model, tgt, tdep, srch, sdep)      # [1,1,h,w]
             emit(x1, batch["target_gt"][j:j + 1], batch["seq_name"][j], batch["frame_index"][j])

@@ -12,6 +12,12 @@ random.Random(seed).sample(range(T), N) per target.  The two paths alternate on 
 sequence; the spread is the (max - min) / mean of a path's own rounds.  A second, separately timed
 pass splits each path into its encoder stage and its head stage with events between the stages
 (the per-target stages are multi_reference_x1's own calls, in its order).  One JSON line.
+
+--coatt mxfp8 runs the bank path's co-attention on MX-fp8 images of the bank (bf16 only; default
+bf16, the indexed bf16 kernel).  The result then also holds the one-off image build of the bank
+(both modalities, timed on its own over the rounds; it is part of the bank's encoder stage) and
+the outputs against the bf16 bank's on the same sequence.  To compare the two settings, alternate
+runs of this tool with --coatt bf16 and --coatt mxfp8 on one device.
 """
 import argparse
 import json
@@ -43,7 +49,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--encode-chunk", type=int, default=8)
     ap.add_argument("--pair-chunk", type=int, default=10)
-    return ap.parse_args()
+    ap.add_argument("--coatt", default="bf16", choices=["bf16", "mxfp8"],
+                    help="the bank path's co-attention (mxfp8: MX-fp8 images, --dtype bf16 only)")
+    a = ap.parse_args()
+    if a.coatt == "mxfp8" and a.dtype != "bf16":
+        ap.error("--coatt mxfp8 needs --dtype bf16")
+    return a
 
 
 def timed(fn):
@@ -109,7 +120,8 @@ def main():
                           for t in range(T)])
 
     def bank():
-        return segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk, pair_chunk=a.pair_chunk)
+        return segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk, pair_chunk=a.pair_chunk,
+                                coatt=a.coatt)
 
     # ---- stage split: the same calls with events between the stages -------------------------------
     @torch.no_grad()
@@ -141,7 +153,7 @@ def main():
     @torch.no_grad()
     def bank_stages(st):
         ia, ib = plan_pairs(T, list(range(T)), refs)
-        b = st.run("encoder", lambda: FeatureBank.encode(m, rgbs, deps, a.encode_chunk))
+        b = st.run("encoder", lambda: FeatureBank.encode(m, rgbs, deps, a.encode_chunk, a.coatt))
         step = max(1, a.pair_chunk // N)
 
         def head():
@@ -168,19 +180,36 @@ def main():
     split_a = {k: v / a.rounds for k, v in sa.totals().items()}
     split_b = {k: v / a.rounds for k, v in sb.totals().items()}
 
+    extra = {}
+    if a.coatt == "mxfp8":
+        with torch.no_grad():
+            b = FeatureBank.encode(m, rgbs, deps, a.encode_chunk)
+            hw = b.geo[1] * b.geo[2]
+            build = lambda: (ops.coatt_f8_bank(b.vat, b.va, T, hw), ops.coatt_f8_bank(b.dat, b.da, T, hw))
+            build()
+            tm = [timed(build)[0] for _ in range(a.rounds)]
+            imgs = build()
+        ref = segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk,
+                               pair_chunk=a.pair_chunk).double().cpu()
+        fm = out_b.double().cpu()
+        extra = {"image_build_ms": {"mean": float(np.mean(tm)), "min": float(np.min(tm)), "max": float(np.max(tm))},
+                 "image_bytes_per_frame_and_modality": imgs[0].numel() // T,
+                 "vs_bf16_bank": {"mask_agreement": float(((fm > 0.5) == (ref > 0.5)).double().mean()),
+                                  "mean_abs_diff": float((fm - ref).abs().mean()),
+                                  "max_abs_diff": float((fm - ref).abs().max())}}
     fa, fb = out_a.double().cpu(), out_b.double().cpu()
     stat = lambda v: {"mean": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v)),
                       "spread": float((np.max(v) - np.min(v)) / np.mean(v))}
     ma, mb = float(np.mean(ta)), float(np.mean(tb))
     res = {
-        "tool": "seq_infer_bench", "frames": T, "nref": N, "size": H, "dtype": a.dtype, "seed": a.seed,
-        "rounds": a.rounds, "warmup": max(1, a.warmup), "encode_chunk": a.encode_chunk,
+        "tool": "seq_infer_bench", "frames": T, "nref": N, "size": H, "dtype": a.dtype, "coatt": a.coatt,
+        "seed": a.seed, "rounds": a.rounds, "warmup": max(1, a.warmup), "encode_chunk": a.encode_chunk,
         "pair_chunk": a.pair_chunk, "device": torch.cuda.get_device_name(0),
         "per_target": {"frames_per_s": T / (ma * 1e-3), "ms_per_sequence": stat(ta),
                        "encoder_ms": split_a["encoder"], "head_ms": split_a["head"],
                        "encoder_passes": T * (1 + N)},
         "bank": {"frames_per_s": T / (mb * 1e-3), "ms_per_sequence": stat(tb),
-                 "encoder_ms": split_b["encoder"], "head_ms": split_b["head"], "encoder_passes": T},
+                 "encoder_ms": split_b["encoder"], "head_ms": split_b["head"], "encoder_passes": T, **extra},
         "speedup": ma / mb,
         # faster by more than the run-to-run spread: the slowest bank round against the fastest
         # per-target round
