@@ -671,8 +671,6 @@ template <class T> int bwd_splits(int P, int C, int* gx) {
   return grid_rows<T>(P, C, gx, g_tune[T_BR_ROWS], g_tune[T_BR_BLOCKS], 1, true);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int cn_bn_set_tuning(int key, int value) {
@@ -682,10 +680,14 @@ extern "C" int cn_bn_set_tuning(int key, int value) {
 }
 
 extern "C" size_t cn_bn_workspace_floats(int dtype, int P, int C, int nseg) {
-  int gx, s_st, s_bw;
-  if (dtype == DT_BF16) { s_st = stat_splits<bf16>(P, C, nseg, &gx); s_bw = bwd_splits<bf16>(P, C, &gx); }
-  else { s_st = stat_splits<float>(P, C, nseg, &gx); s_bw = bwd_splits<float>(P, C, &gx); }
-  size_t a = (size_t)nseg * 2 * s_st, b = (size_t)3 * s_bw;
+  size_t a = 0, b = 0;  // an unsupported dtype has no workspace
+  with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    int gx;
+    a = (size_t)nseg * 2 * stat_splits<T>(P, C, nseg, &gx);
+    b = (size_t)3 * bwd_splits<T>(P, C, &gx);
+    return 0;
+  });
   return (a > b ? a : b) * C;
 }
 
@@ -715,13 +717,13 @@ static int bn_stats_launch(const T* x, long long ldx, int P, int nseg, int C, fl
 extern "C" int cn_bn_stats(int dtype, const void* x, long long ldx, int P, int nseg, int C,
                            float* mean, float* invstd, float* run_mean, float* run_var,
                            float momentum, float eps, float* ws, hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4) || ldx % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  if (P < 1 || nseg < 1) return CN_ERR_SHAPE;
-  if (dtype == DT_BF16)
-    return bn_stats_launch<bf16>((const bf16*)x, ldx, P, nseg, C, mean, invstd, run_mean, run_var,
-                                 momentum, eps, ws, st);
-  return bn_stats_launch<float>((const float*)x, ldx, P, nseg, C, mean, invstd, run_mean, run_var,
-                                momentum, eps, ws, st);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % VecOf<T>::N || ldx % VecOf<T>::N) return CN_ERR_ALIGN;
+    if (P < 1 || nseg < 1) return CN_ERR_SHAPE;
+    return bn_stats_launch<T>((const T*)x, ldx, P, nseg, C, mean, invstd, run_mean, run_var, momentum,
+                              eps, ws, st);
+  });
 }
 
 int cn_bn_tile_stats_impl(const float* ws, long long plane, int mtiles, int BM, int M, int nseg, int C,
@@ -758,29 +760,23 @@ extern "C" int cn_bn_bwd_apply(int dtype, const void* x, long long ldx, const vo
                                int P, int C, const float* mean, const float* invstd,
                                const float* gamma, const float* beta, const float* sum_dz,
                                const float* sum_dzxh, void* dx, long long lddx, hipStream_t st) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  if (C % vec || ldx % vec || lddy % vec || lddx % vec) return CN_ERR_ALIGN;
-  if (!aligned16(mean) || !aligned16(invstd) || !aligned16(gamma) || !aligned16(beta) ||
-      !aligned16(sum_dz) || !aligned16(sum_dzxh))
-    return CN_ERR_ALIGN;
-  if (P < 1) return CN_ERR_SHAPE;
-  int gx, gy;
-  // act 3: ReLU mask recomputed from x with the forward's affine (no residual on these BNs)
-  if (dtype == DT_BF16) {
-    gy = grid_rows<bf16>(P, C, &gx, g_tune[T_BA_ROWS], g_tune[T_BA_BLOCKS]);
-    hipLaunchKernelGGL(bn_bwd_apply_k<bf16>, dim3(gx, gy), dim3(256), 0, st, (const bf16*)x, ldx,
-                       (const bf16*)dy, lddy, (const bf16*)nullptr, 0ll, (const unsigned char*)nullptr, P, C, mean, invstd, gamma,
-                       beta, 3, (const float*)nullptr, sum_dz, sum_dzxh, (bf16*)dx, lddx,
-                       (bf16*)nullptr, 0ll, bn_wt(P, lddx, 2));
-  } else {
-    gy = grid_rows<float>(P, C, &gx, g_tune[T_BA_ROWS], g_tune[T_BA_BLOCKS]);
-    hipLaunchKernelGGL(bn_bwd_apply_k<float>, dim3(gx, gy), dim3(256), 0, st, (const float*)x, ldx,
-                       (const float*)dy, lddy, (const float*)nullptr, 0ll, (const unsigned char*)nullptr, P, C, mean, invstd, gamma,
-                       beta, 3, (const float*)nullptr, sum_dz, sum_dzxh, (float*)dx, lddx,
-                       (float*)nullptr, 0ll, bn_wt(P, lddx, 4));
-  }
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int vec = VecOf<T>::N;
+    if (C % vec || ldx % vec || lddy % vec || lddx % vec) return CN_ERR_ALIGN;
+    if (misaligned(mean) || misaligned(invstd) || misaligned(gamma) || misaligned(beta) ||
+        misaligned(sum_dz) || misaligned(sum_dzxh))
+      return CN_ERR_ALIGN;
+    if (P < 1) return CN_ERR_SHAPE;
+    int gx, gy = grid_rows<T>(P, C, &gx, g_tune[T_BA_ROWS], g_tune[T_BA_BLOCKS]);
+    // act 3: ReLU mask recomputed from x with the forward's affine (no residual on these BNs)
+    hipLaunchKernelGGL(bn_bwd_apply_k<T>, dim3(gx, gy), dim3(256), 0, st, (const T*)x, ldx,
+                       (const T*)dy, lddy, (const T*)nullptr, 0ll, (const unsigned char*)nullptr, P, C,
+                       mean, invstd, gamma, beta, 3, (const float*)nullptr, sum_dz, sum_dzxh, (T*)dx,
+                       lddx, (T*)nullptr, 0ll, bn_wt(P, lddx, (int)sizeof(T)));
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_bn_eval_params(const float* run_mean, const float* run_var, int C, float eps,
@@ -827,31 +823,26 @@ extern "C" int cn_bn_apply_ex(int dtype, const void* x, long long ldx, int P, in
                               const float* rgamma, const float* rbeta, int act, const float* prelu,
                               void* y, long long ldy, void* y8, long long ldy8, float* qstate,
                               unsigned char* mask, long long ldm, hipStream_t st) {
-  if (y8 && (dtype != DT_BF16 || !qstate || ldy8 % 16 || ((uintptr_t)y8 & 7))) return CN_ERR_ALIGN;
-  if (mask && ldm < C / (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_SHAPE;
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  if (C % vec || ldx % vec || ldy % vec || (res && ldr % vec) || (xr && ldxr % vec)) return CN_ERR_ALIGN;
-  if (!aligned16(mean) || !aligned16(invstd) || !aligned16(gamma) || !aligned16(beta) ||
-      !aligned16(rmean) || !aligned16(rinvstd) || !aligned16(rgamma) || !aligned16(rbeta))
-    return CN_ERR_ALIGN;
-  if (P < 1 || nseg < 1) return CN_ERR_SHAPE;
-  const int wt = bn_wt((long long)nseg * P, ldy, dtype == DT_BF16 ? 2 : 4);
-  int gx, gy;
-  if (dtype == DT_BF16) {
-    gy = grid_rows<bf16>(P, C, &gx, g_tune[T_AP_ROWS], g_tune[T_AP_BLOCKS], nseg);
-    hipLaunchKernelGGL(bn_apply_k<bf16>, dim3(gx, gy, nseg), dim3(256), 0, st, (const bf16*)x, ldx, P, C,
-                       mean, invstd, gamma, beta, (const bf16*)res, ldr, (const bf16*)xr, ldxr, rmean,
-                       rinvstd, rgamma, rbeta, act, prelu, (bf16*)y, ldy, (unsigned char*)y8, ldy8,
-                       qstate, mask, ldm, wt);
-  } else {
-    gy = grid_rows<float>(P, C, &gx, g_tune[T_AP_ROWS], g_tune[T_AP_BLOCKS], nseg);
-    hipLaunchKernelGGL(bn_apply_k<float>, dim3(gx, gy, nseg), dim3(256), 0, st, (const float*)x, ldx, P, C,
-                       mean, invstd, gamma, beta, (const float*)res, ldr, (const float*)xr, ldxr,
-                       rmean, rinvstd, rgamma, rbeta, act, prelu, (float*)y, ldy,
-                       (unsigned char*)nullptr, 0ll, (float*)nullptr, mask, ldm, wt);
-  }
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int vec = VecOf<T>::N;
+    // the fp8 copy exists for bf16 only, so with fp32 the kernel gets a null y8 and ignores qstate
+    if (y8 && (dtype != DT_BF16 || !qstate || ldy8 % 16 || misaligned(y8, 8))) return CN_ERR_ALIGN;
+    if (mask && ldm < C / vec) return CN_ERR_SHAPE;
+    if (C % vec || ldx % vec || ldy % vec || (res && ldr % vec) || (xr && ldxr % vec)) return CN_ERR_ALIGN;
+    if (misaligned(mean) || misaligned(invstd) || misaligned(gamma) || misaligned(beta) ||
+        misaligned(rmean) || misaligned(rinvstd) || misaligned(rgamma) || misaligned(rbeta))
+      return CN_ERR_ALIGN;
+    if (P < 1 || nseg < 1) return CN_ERR_SHAPE;
+    const int wt = bn_wt((long long)nseg * P, ldy, (int)sizeof(T));
+    int gx, gy = grid_rows<T>(P, C, &gx, g_tune[T_AP_ROWS], g_tune[T_AP_BLOCKS], nseg);
+    hipLaunchKernelGGL(bn_apply_k<T>, dim3(gx, gy, nseg), dim3(256), 0, st, (const T*)x, ldx, P, C, mean,
+                       invstd, gamma, beta, (const T*)res, ldr, (const T*)xr, ldxr, rmean, rinvstd,
+                       rgamma, rbeta, act, prelu, (T*)y, ldy, (unsigned char*)y8, ldy8, qstate, mask,
+                       ldm, wt);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 template <class T>
@@ -892,20 +883,19 @@ extern "C" int cn_bn_bwd(int dtype, const void* x, long long ldx, const void* dy
                          const float* prelu, float* dgamma, float* dbeta, float* dprelu_c,
                          void* dx, long long lddx, void* dres, long long lddres, float* ws,
                          hipStream_t st) {
-  const int vec = dtype == DT_BF16 ? 8 : 4;
-  if (C % vec || ldx % vec || lddy % vec || (y && act != 4 && ldy % vec) || (dx && lddx % vec) ||
-      (dres && lddres % vec))
-    return CN_ERR_ALIGN;
-  if (act == 4 && (!y || ldy < C / vec)) return CN_ERR_SHAPE;
-  if (!aligned16(mean) || !aligned16(invstd) || !aligned16(gamma) || !aligned16(beta) ||
-      !aligned16(dgamma) || !aligned16(dbeta))
-    return CN_ERR_ALIGN;
-  if (P < 1) return CN_ERR_SHAPE;
-  if (dtype == DT_BF16)
-    return bn_bwd_launch<bf16>((const bf16*)x, ldx, (const bf16*)dy, lddy, (const bf16*)y, ldy, P, C,
-                               mean, invstd, gamma, beta, act, prelu, dgamma, dbeta, dprelu_c,
-                               (bf16*)dx, lddx, (bf16*)dres, lddres, ws, st);
-  return bn_bwd_launch<float>((const float*)x, ldx, (const float*)dy, lddy, (const float*)y, ldy, P, C,
-                              mean, invstd, gamma, beta, act, prelu, dgamma, dbeta, dprelu_c,
-                              (float*)dx, lddx, (float*)dres, lddres, ws, st);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int vec = VecOf<T>::N;
+    if (C % vec || ldx % vec || lddy % vec || (y && act != 4 && ldy % vec) || (dx && lddx % vec) ||
+        (dres && lddres % vec))
+      return CN_ERR_ALIGN;
+    if (act == 4 && (!y || ldy < C / vec)) return CN_ERR_SHAPE;
+    if (misaligned(mean) || misaligned(invstd) || misaligned(gamma) || misaligned(beta) ||
+        misaligned(dgamma) || misaligned(dbeta))
+      return CN_ERR_ALIGN;
+    if (P < 1) return CN_ERR_SHAPE;
+    return bn_bwd_launch<T>((const T*)x, ldx, (const T*)dy, lddy, (const T*)y, ldy, P, C, mean, invstd,
+                            gamma, beta, act, prelu, dgamma, dbeta, dprelu_c, (T*)dx, lddx, (T*)dres,
+                            lddres, ws, st);
+  });
 }

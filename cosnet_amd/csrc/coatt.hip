@@ -153,45 +153,45 @@ __global__ __launch_bounds__(256) void dscore_k(const T* __restrict__ Pc, const 
 
 }  // namespace
 
+// cn_coatt_softmax's workspace: RS row-split partials of the column statistics (max and sum per
+// column), then the column max `cm` and reciprocal sum `rcl`.
+struct ColStatWs { float *part, *cm, *rcl; size_t floats; };
+static constexpr int RS = 16;
+static ColStatWs colstat_layout(int B, int ld, float* ws) {
+  const size_t part = (size_t)RS * B * ld * 2, col = (size_t)B * ld;
+  return {ws, ws + part, ws + part + col, part + 2 * col};
+}
+
 extern "C" size_t cn_coatt_workspace_floats(int B, int HW, int ld) {
-  // column-stat partials (RS=16 splits) + cm + rcl
-  return (size_t)16 * B * ld * 2 + (size_t)2 * B * ld;
+  return colstat_layout(B, ld, nullptr).floats;
 }
 
 extern "C" int cn_coatt_softmax(int dtype, const float* S, int B, int HW, int ld, void* Pc, void* PT,
                                 float* ws, hipStream_t st) {
-  if (ld % 8 || ld < HW) return CN_ERR_ALIGN;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(softmax_rows_k<bf16>, dim3(B * HW), dim3(256), 0, st, S, HW, ld, (bf16*)Pc);
-  else
-    hipLaunchKernelGGL(softmax_rows_k<float>, dim3(B * HW), dim3(256), 0, st, S, HW, ld, (float*)Pc);
-  CN_CHECK_LAUNCH();
-  if (!PT) return 0;
-  const int RS = 16;
-  float* part = ws;
-  float* cm = ws + (size_t)RS * B * ld * 2;
-  float* rcl = cm + (size_t)B * ld;
-  hipLaunchKernelGGL(col_stats_partial_k, dim3((HW + 63) / 64, B, RS), dim3(256), 0, st, S, HW, ld, RS, part);
-  CN_CHECK_LAUNCH();
-  hipLaunchKernelGGL(col_stats_final_k, dim3((HW + 255) / 256, B), dim3(256), 0, st, part, B, HW, ld, RS, cm, rcl);
-  CN_CHECK_LAUNCH();
-  dim3 grid((HW + 63) / 64, (ld + 63) / 64, B);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(prow_trans_k<bf16>, grid, dim3(256), 0, st, S, HW, ld, cm, rcl, (bf16*)PT);
-  else
-    hipLaunchKernelGGL(prow_trans_k<float>, grid, dim3(256), 0, st, S, HW, ld, cm, rcl, (float*)PT);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (ld % 8 || ld < HW) return CN_ERR_ALIGN;
+    hipLaunchKernelGGL(softmax_rows_k<T>, dim3(B * HW), dim3(256), 0, st, S, HW, ld, (T*)Pc);
+    CN_CHECK_LAUNCH();
+    if (!PT) return 0;
+    const ColStatWs w = colstat_layout(B, ld, ws);
+    hipLaunchKernelGGL(col_stats_partial_k, dim3((HW + 63) / 64, B, RS), dim3(256), 0, st, S, HW, ld, RS, w.part);
+    CN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(col_stats_final_k, dim3((HW + 255) / 256, B), dim3(256), 0, st, w.part, B, HW, ld, RS, w.cm, w.rcl);
+    CN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(prow_trans_k<T>, dim3((HW + 63) / 64, (ld + 63) / 64, B), dim3(256), 0, st, S, HW, ld, w.cm, w.rcl, (T*)PT);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_coatt_dscore(int dtype, const void* Pc, const float* dPc, const float* d1,
                                const void* PT, const float* dPr, const float* d2, int B, int HW,
                                int ld, void* dS, hipStream_t st) {
-  dim3 grid((ld + 63) / 64, (HW + 63) / 64, B);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(dscore_k<bf16>, grid, dim3(256), 0, st, (const bf16*)Pc, dPc, d1, (const bf16*)PT, dPr, d2, HW, ld, (bf16*)dS);
-  else
-    hipLaunchKernelGGL(dscore_k<float>, grid, dim3(256), 0, st, (const float*)Pc, dPc, d1, (const float*)PT, dPr, d2, HW, ld, (float*)dS);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    hipLaunchKernelGGL(dscore_k<T>, dim3((ld + 63) / 64, (HW + 63) / 64, B), dim3(256), 0, st, (const T*)Pc, dPc, d1, (const T*)PT, dPr, d2, HW, ld, (T*)dS);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }

@@ -26,6 +26,7 @@
 //          32-channel block, block dt): lane half h reads block u = h.
 // Padded rows / keys (>= HW) are zeros, so the loads need no bounds checks.
 #include "common.h"
+#include "coatt_fused.h"
 #include "../../include/cosnet_hip.h"
 
 namespace {
@@ -510,12 +511,49 @@ static inline int hwp64(int HW) { return (HW + KT - 1) / KT * KT; }
 // row images hold whole 128-row query blocks (rows >= HW are zeros), so the last block's Q
 // loads stay inside its own batch entry's image
 static inline int hwq128(int HW) { return (HW + QB - 1) / QB * QB; }
+static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// workspace: two row images (Va_t, Vb) + two V^T images (Vb, Va), each with its scales
-extern "C" size_t cn_coatt_f8_workspace_bytes(int B, int HW) {
-  const size_t rows = (size_t)B * hwq128(HW);
-  const size_t nt = (size_t)hwp64(HW) / KT;
-  return 2 * rows * (D + 8) + 2 * (size_t)B * nt * (VBYTES + 512) + 256;
+// Dense workspace: two row images (Va_t, Vb) with their scales, then -- 256-byte aligned, the one
+// round-up, whose slack the total carries in full -- two V^T images (Vb, Va) and their scales.
+struct F8Dense { unsigned char *a8, *b8, *as, *bs, *vtb, *vta, *vtbs, *vtas; size_t bytes; };
+static F8Dense f8_dense_layout(void* ws, int B, int HW) {
+  const size_t rows = (size_t)B * hwq128(HW), tiles = (size_t)B * (hwp64(HW) / KT);
+  unsigned char* p = (unsigned char*)ws;
+  size_t o = 0;
+  F8Dense k;
+  k.a8 = p + o;   o += rows * D;
+  k.b8 = p + o;   o += rows * D;
+  k.as = p + o;   o += rows * 8;
+  k.bs = p + o;   o += rows * 8;
+  k.bytes = o + 2 * tiles * (VBYTES + 512) + 256;
+  o = al256(o);
+  k.vtb = p + o;  o += tiles * VBYTES;
+  k.vta = p + o;  o += tiles * VBYTES;
+  k.vtbs = p + o; o += tiles * 512;
+  k.vtas = p + o;
+  return k;
+}
+
+extern "C" size_t cn_coatt_f8_workspace_bytes(int B, int HW) { return f8_dense_layout(nullptr, B, HW).bytes; }
+extern "C" size_t cn_coatt_f8_train_workspace_bytes(int B, int HW) {
+  return cn_coatt_f8_workspace_bytes(B, HW);   // the prepass keeps its block exponents in LDS
+}
+
+// bf16 operand rows: whole 16-byte chunks from a 16-byte aligned base; a workspace or image: present,
+// 256-byte aligned, large enough
+static bool f8_rows_ok(const void* x, long long ld) { return ld % 8 == 0 && !misaligned(x); }
+static bool f8_buf_ok(const void* p, size_t bytes, size_t need) {
+  return p && !misaligned(p, 256) && bytes >= need;
+}
+
+// The attention launch over filled a.dir[0 .. ndir): geometry of `pairs` pairs, then the kernel.
+static int f8_launch(F8Args& a, int HW, int ndir, int pairs, hipStream_t st) {
+  a.HW = HW; a.HWp = hwq128(HW); a.HWp32 = hw_pad32(HW); a.nt = hwp64(HW) / KT; a.ndir = ndir;
+  a.nrb = (HW + QB - 1) / QB;
+  a.nitems = a.nrb * pairs * ndir;
+  hipLaunchKernelGGL(coatt_f8_fwd_k, dim3((a.nitems + 7) & ~7), dim3(256), 0, st, a);
+  CN_CHECK_LAUNCH();
+  return 0;
 }
 
 // Z_a, Z_b (bf16) of the co-attention with MX-fp8 operands; lse_a / lse_b (optional, [B][HWp32],
@@ -523,24 +561,50 @@ extern "C" size_t cn_coatt_f8_workspace_bytes(int B, int HW) {
 static int f8_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
                   const void* vb, long long ld_vb, int B, int HW, void* za, void* zb, long long ld_z,
                   float* lse_a, float* lse_b, void* ws, bool train, void* vat_q, void* va_q,
-                  void* vb_q, long long ld_q, hipStream_t st);
+                  void* vb_q, long long ld_q, hipStream_t st) {
+  const int HWp = hwq128(HW), nt = hwp64(HW) / KT;
+  const F8Dense k = f8_dense_layout(ws, B, HW);
+  if (train) {   // one launch: all three operands' images and decoded copies
+    F8Prep pa = {};
+    pa.x[0] = (const bf16*)vat; pa.x[1] = (const bf16*)vb; pa.x[2] = (const bf16*)va;
+    pa.ldx[0] = ld_vat; pa.ldx[1] = ld_vb; pa.ldx[2] = ld_va;
+    pa.x8[0] = k.a8; pa.xs[0] = k.as; pa.x8[1] = k.b8; pa.xs[1] = k.bs;
+    pa.vt8[0] = k.vtb; pa.vts[0] = k.vtbs; pa.vt8[1] = k.vta; pa.vts[1] = k.vtas;
+    pa.dq[0] = (bf16*)vat_q; pa.dq[1] = (bf16*)vb_q; pa.dq[2] = (bf16*)va_q; pa.lddq = ld_q;
+    pa.B = B; pa.HW = HW; pa.HWp = HWp; pa.nt = nt;
+    hipLaunchKernelGGL(coatt_f8_prep_k, dim3((unsigned)(B * (HWp / 32)), 3), dim3(256), 0, st, pa);
+    CN_CHECK_LAUNCH();
+  } else {
+    const long long nr = (long long)B * HWp * 8, nv = (long long)B * nt * 2 * D;
+    const dim3 gr((unsigned)((nr + 255) / 256)), gv((unsigned)((nv + 255) / 256));
+    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vat, ld_vat, B, HW, HWp, k.a8, k.as);
+    CN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, HWp, k.b8, k.bs);
+    CN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, nt, k.vtb, k.vtbs);
+    CN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)va, ld_va, B, HW, nt, k.vta, k.vtas);
+    CN_CHECK_LAUNCH();
+  }
+  F8Args a = {};
+  // direction 0: Z_a = softmax_j(S) Vb  (queries Va_t, keys Vb, values Vb)
+  a.dir[0] = F8Dir{k.a8, k.as, k.b8, k.bs, k.vtb, k.vtbs, (bf16*)za, ld_z, lse_a};
+  // direction 1: Z_b = softmax_i(S)^T Va  (queries Vb, keys Va_t, values Va)
+  a.dir[1] = F8Dir{k.b8, k.bs, k.a8, k.as, k.vta, k.vtas, (bf16*)zb, ld_z, lse_b};
+  return f8_launch(a, HW, 2, B, st);
+}
 
 extern "C" int cn_coatt_f8_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
                                const void* vb, long long ld_vb, int B, int HW, int C, void* za,
                                void* zb, long long ld_z, float* lse_a, float* lse_b, void* ws,
                                size_t ws_bytes, hipStream_t st) {
   if (B <= 0 || HW <= 0 || C != D || !za || !zb) return CN_ERR_SHAPE;
-  if (ld_vat % 8 || ld_va % 8 || ld_vb % 8 || ld_z % 4) return CN_ERR_ALIGN;
-  if (((uintptr_t)vat & 15) || ((uintptr_t)va & 15) || ((uintptr_t)vb & 15) || ((uintptr_t)za & 7) ||
-      ((uintptr_t)zb & 7))
+  if (!f8_rows_ok(vat, ld_vat) || !f8_rows_ok(va, ld_va) || !f8_rows_ok(vb, ld_vb) || ld_z % 4 ||
+      misaligned(za, 8) || misaligned(zb, 8))
     return CN_ERR_ALIGN;
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < cn_coatt_f8_workspace_bytes(B, HW)) return CN_ERR_SHAPE;
+  if (!f8_buf_ok(ws, ws_bytes, cn_coatt_f8_workspace_bytes(B, HW))) return CN_ERR_SHAPE;
   return f8_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, za, zb, ld_z, lse_a, lse_b, ws, false,
                 nullptr, nullptr, nullptr, 0, st);
-}
-
-extern "C" size_t cn_coatt_f8_train_workspace_bytes(int B, int HW) {
-  return cn_coatt_f8_workspace_bytes(B, HW);   // the prepass keeps its block exponents in LDS
 }
 
 extern "C" int cn_coatt_f8_train_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
@@ -550,66 +614,13 @@ extern "C" int cn_coatt_f8_train_fwd(const void* vat, long long ld_vat, const vo
                                      size_t ws_bytes, hipStream_t st) {
   if (B <= 0 || HW <= 0 || C != D || !za || !zb || !lse_a || !lse_b || !vat_q || !va_q || !vb_q)
     return CN_ERR_SHAPE;
-  if (ld_vat % 8 || ld_va % 8 || ld_vb % 8 || ld_z % 4 || ld_q % 8 || ld_q < C) return CN_ERR_ALIGN;
-  if (((uintptr_t)vat & 15) || ((uintptr_t)va & 15) || ((uintptr_t)vb & 15) || ((uintptr_t)za & 7) ||
-      ((uintptr_t)zb & 7) || ((uintptr_t)vat_q & 15) || ((uintptr_t)va_q & 15) || ((uintptr_t)vb_q & 15))
+  if (!f8_rows_ok(vat, ld_vat) || !f8_rows_ok(va, ld_va) || !f8_rows_ok(vb, ld_vb) || ld_z % 4 ||
+      misaligned(za, 8) || misaligned(zb, 8) || ld_q % 8 || ld_q < C || misaligned(vat_q) ||
+      misaligned(va_q) || misaligned(vb_q))
     return CN_ERR_ALIGN;
-  if (!ws || ((uintptr_t)ws & 255) || ws_bytes < cn_coatt_f8_train_workspace_bytes(B, HW)) return CN_ERR_SHAPE;
+  if (!f8_buf_ok(ws, ws_bytes, cn_coatt_f8_train_workspace_bytes(B, HW))) return CN_ERR_SHAPE;
   return f8_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, B, HW, za, zb, ld_z, lse_a, lse_b, ws, true,
                 vat_q, va_q, vb_q, ld_q, st);
-}
-
-static int f8_fwd(const void* vat, long long ld_vat, const void* va, long long ld_va,
-                  const void* vb, long long ld_vb, int B, int HW, void* za, void* zb, long long ld_z,
-                  float* lse_a, float* lse_b, void* ws, bool train, void* vat_q, void* va_q,
-                  void* vb_q, long long ld_q, hipStream_t st) {
-  const int HWp = hwq128(HW), nt = hwp64(HW) / KT;
-  const size_t rows = (size_t)B * HWp;
-  unsigned char* p = (unsigned char*)ws;
-  unsigned char* a8 = p;              p += rows * D;
-  unsigned char* b8 = p;              p += rows * D;
-  unsigned char* as = p;              p += rows * 8;
-  unsigned char* bs = p;              p += rows * 8;
-  p = (unsigned char*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-  unsigned char* vtb = p;             p += (size_t)B * nt * VBYTES;
-  unsigned char* vta = p;             p += (size_t)B * nt * VBYTES;
-  unsigned char* vtbs = p;            p += (size_t)B * nt * 512;
-  unsigned char* vtas = p;
-  const long long nr = (long long)rows * 8;
-  const dim3 gr((unsigned)((nr + 255) / 256));
-  if (train) {   // one launch: all three operands' images and decoded copies
-    F8Prep pa = {};
-    pa.x[0] = (const bf16*)vat; pa.x[1] = (const bf16*)vb; pa.x[2] = (const bf16*)va;
-    pa.ldx[0] = ld_vat; pa.ldx[1] = ld_vb; pa.ldx[2] = ld_va;
-    pa.x8[0] = a8; pa.xs[0] = as; pa.x8[1] = b8; pa.xs[1] = bs;
-    pa.vt8[0] = vtb; pa.vts[0] = vtbs; pa.vt8[1] = vta; pa.vts[1] = vtas;
-    pa.dq[0] = (bf16*)vat_q; pa.dq[1] = (bf16*)vb_q; pa.dq[2] = (bf16*)va_q; pa.lddq = ld_q;
-    pa.B = B; pa.HW = HW; pa.HWp = HWp; pa.nt = nt;
-    hipLaunchKernelGGL(coatt_f8_prep_k, dim3((unsigned)(B * (HWp / 32)), 3), dim3(256), 0, st, pa);
-    CN_CHECK_LAUNCH();
-  } else {
-    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vat, ld_vat, B, HW, HWp, a8, as);
-    CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(coatt_f8_rows_k, gr, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, HWp, b8, bs);
-    CN_CHECK_LAUNCH();
-    const long long nv = (long long)B * nt * 2 * D;
-    const dim3 gv((unsigned)((nv + 255) / 256));
-    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)vb, ld_vb, B, HW, nt, vtb, vtbs);
-    CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(coatt_f8_vt_k, gv, dim3(256), 0, st, (const bf16*)va, ld_va, B, HW, nt, vta, vtas);
-    CN_CHECK_LAUNCH();
-  }
-  F8Args a = {};
-  // direction 0: Z_a = softmax_j(S) Vb  (queries Va_t, keys Vb, values Vb)
-  a.dir[0] = F8Dir{a8, as, b8, bs, vtb, vtbs, (bf16*)za, ld_z, lse_a};
-  // direction 1: Z_b = softmax_i(S)^T Va  (queries Vb, keys Va_t, values Va)
-  a.dir[1] = F8Dir{b8, bs, a8, as, vta, vtas, (bf16*)zb, ld_z, lse_b};
-  a.HW = HW; a.HWp = HWp; a.HWp32 = (HW + 31) / 32 * 32; a.nt = nt; a.ndir = 2;
-  a.nrb = (HW + QB - 1) / QB;
-  a.nitems = a.nrb * B * 2;
-  hipLaunchKernelGGL(coatt_f8_fwd_k, dim3((a.nitems + 7) & ~7), dim3(256), 0, st, a);
-  CN_CHECK_LAUNCH();
-  return 0;
 }
 
 // ---- MX image bank (whole-sequence inference) ---------------------------------------------------
@@ -618,12 +629,7 @@ static int f8_fwd(const void* vat, long long ld_vat, const void* va, long long l
 // what the inference prepass above writes for it (an MX image is a function of its own frame's
 // rows only).  Sub-buffers are 256-byte aligned.
 namespace {
-struct F8Bank {
-  unsigned char* q8; unsigned char* k8; unsigned char* qs; unsigned char* ks;
-  unsigned char* vt8; unsigned char* vts;
-  size_t bytes;
-};
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct F8Bank { unsigned char *q8, *k8, *qs, *ks, *vt8, *vts; size_t bytes; };
 inline F8Bank f8_bank_layout(void* img, int T, int HW) {
   const size_t rows = (size_t)T * hwq128(HW);
   const size_t tiles = (size_t)T * (hwp64(HW) / KT);
@@ -642,17 +648,15 @@ inline F8Bank f8_bank_layout(void* img, int T, int HW) {
 }  // namespace
 
 extern "C" size_t cn_coatt_f8_bank_bytes(int T, int HW) {
-  if (T <= 0 || HW <= 0) return 0;
-  return f8_bank_layout(nullptr, T, HW).bytes;
+  return T <= 0 || HW <= 0 ? 0 : f8_bank_layout(nullptr, T, HW).bytes;
 }
 
 extern "C" int cn_coatt_f8_bank_build(const void* vat, long long ld_vat, const void* va, long long ld_va,
                                       int T, int HW, int C, void* img, size_t img_bytes,
                                       hipStream_t st) {
   if (T <= 0 || HW <= 0 || C != D || !vat || !va) return CN_ERR_SHAPE;
-  if (ld_vat % 8 || ld_va % 8 || ld_vat < C || ld_va < C) return CN_ERR_ALIGN;
-  if (((uintptr_t)vat & 15) || ((uintptr_t)va & 15)) return CN_ERR_ALIGN;
-  if (!img || ((uintptr_t)img & 255) || img_bytes < cn_coatt_f8_bank_bytes(T, HW)) return CN_ERR_SHAPE;
+  if (!f8_rows_ok(vat, ld_vat) || !f8_rows_ok(va, ld_va) || ld_vat < C || ld_va < C) return CN_ERR_ALIGN;
+  if (!f8_buf_ok(img, img_bytes, cn_coatt_f8_bank_bytes(T, HW))) return CN_ERR_SHAPE;
   const int HWp = hwq128(HW), nt = hwp64(HW) / KT;
   const long long nr = (long long)T * HWp * 8, nv = (long long)T * nt * 2 * D;
   if ((nr + 255) / 256 > 0x7fffffffll || (nv + 255) / 256 > 0x7fffffffll) return CN_ERR_SHAPE;
@@ -677,7 +681,7 @@ extern "C" int cn_coatt_f8_fwd_idx(const void* img0, const void* img1, int T, co
   if ((img1 == nullptr) != (za1 == nullptr)) return CN_ERR_SHAPE;
   if ((!ia || !ib) && P > T) return CN_ERR_SHAPE;
   if (ld_z % 4 || ld_z < C) return CN_ERR_ALIGN;
-  if (((uintptr_t)img0 & 255) || ((uintptr_t)img1 & 255) || ((uintptr_t)za0 & 7) || ((uintptr_t)za1 & 7))
+  if (misaligned(img0, 256) || misaligned(img1, 256) || misaligned(za0, 8) || misaligned(za1, 8))
     return CN_ERR_ALIGN;
   const int ndir = img1 ? 2 : 1;
   const int nrb = (HW + QB - 1) / QB;
@@ -690,10 +694,5 @@ extern "C" int cn_coatt_f8_fwd_idx(const void* img0, const void* img1, int T, co
     // queries Va_t[ia], keys and values Va[ib]
     a.dir[m] = F8Dir{k.q8, k.qs, k.k8, k.ks, k.vt8, k.vts, (bf16*)zs[m], ld_z, nullptr, ia, ib};
   }
-  a.HW = HW; a.HWp = hwq128(HW); a.HWp32 = (HW + 31) / 32 * 32; a.nt = hwp64(HW) / KT; a.ndir = ndir;
-  a.nrb = nrb;
-  a.nitems = nrb * P * ndir;
-  hipLaunchKernelGGL(coatt_f8_fwd_k, dim3((a.nitems + 7) & ~7), dim3(256), 0, st, a);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return f8_launch(a, HW, ndir, P, st);
 }

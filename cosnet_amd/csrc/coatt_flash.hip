@@ -19,6 +19,7 @@
 // lane-locally and, packed to bf16, is directly the B operand of dVa_t^T += Vb^T dS^T (Vb^T
 // fragments by ds_read_b64_tr_b16 from the transposed image).
 #include "common.h"
+#include "coatt_fused.h"
 #include "../../include/cosnet_hip.h"
 
 namespace {
@@ -342,24 +343,18 @@ __global__ __launch_bounds__(256) void dvat_sum_k(const float* __restrict__ part
   for (int e = 0; e < 8; ++e) op[e] = (bf16)acc[e];
 }
 
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// Key splits for `items` workgroups when they leave CUs idle (one workgroup per CU): up to
-// 256 / items splits of >= 16 key tiles each.
-int bwd_nsplit(int items, int ntiles) {
-  if (items >= 256) return 1;
-  int s = 256 / items;
-  if (s > 8) s = 8;
-  while (s > 1 && ntiles / s < 16) --s;
-  return s;
+// The key split of the dVa_t pass and its fp32 partials [nsplit][B * HW][BD], which are the whole
+// workspace: key_splits over the row blocks when they leave CUs idle, else unsplit and no bytes.
+struct BwdSplit { int nsplit; size_t bytes; };
+BwdSplit bwd_split(int B, int HW) {
+  const int items = ((HW + BQ - 1) / BQ) * B;
+  const int s = items >= 256 ? 1 : key_splits(items, (HW + BK - 1) / BK);
+  return {s, s > 1 ? (size_t)s * B * HW * BD * sizeof(float) : 0};
 }
 
 }  // namespace
 
-extern "C" size_t cn_coatt_flash_bwd_workspace_bytes(int B, int HW) {
-  const int s = bwd_nsplit(((HW + BQ - 1) / BQ) * B, (HW + BK - 1) / BK);
-  return s > 1 ? (size_t)s * B * HW * BD * sizeof(float) : 0;
-}
+extern "C" size_t cn_coatt_flash_bwd_workspace_bytes(int B, int HW) { return bwd_split(B, HW).bytes; }
 
 extern "C" int cn_coatt_flash_dvat_ws(const void* vat, long long ld_vat, const void* va, long long ld_va,
                                       const void* dza, long long ld_dza, const void* vb, long long ld_vb,
@@ -391,8 +386,8 @@ extern "C" int cn_coatt_flash_dvat_ws(const void* vat, long long ld_vat, const v
   for (long long ld : {ld_vat, ld_vb, t0 ? ld_dza : (long long)C, t1 ? ld_dzb : (long long)C, t1 ? ld_va : (long long)C})
     if (ld % 8 || ld < C) return CN_ERR_ALIGN;
   if (ld_out % 4 || ld_out < C) return CN_ERR_ALIGN;
-  if (!al16(vat) || !al16(vb) || (t0 && !al16(dza)) || (t1 && (!al16(dzb) || !al16(va) || !al16(lse_b) || !al16(d1))) ||
-      ((uintptr_t)out & 7))
+  if (misaligned(vat) || misaligned(vb) || (t0 && misaligned(dza)) ||
+      (t1 && (misaligned(dzb) || misaligned(va) || misaligned(lse_b) || misaligned(d1))) || misaligned(out, 8))
     return CN_ERR_ALIGN;
   BwdArgs a;
   a.vat = (const bf16*)vat; a.va = (const bf16*)va; a.dza = (const bf16*)dza;
@@ -400,14 +395,13 @@ extern "C" int cn_coatt_flash_dvat_ws(const void* vat, long long ld_vat, const v
   a.ld_vat = ld_vat; a.ld_va = ld_va; a.ld_dza = ld_dza; a.ld_vb = ld_vb; a.ld_dzb = ld_dzb;
   a.lse_a = lse_a; a.d0 = d0; a.lse_b = lse_b; a.d1 = d1;
   a.out = (bf16*)out; a.ld_out = ld_out;
-  a.HW = HW; a.HWp = (HW + 31) / 32 * 32;
+  a.HW = HW; a.HWp = hw_pad32(HW);
   a.nrb = (HW + BQ - 1) / BQ;
   const int ntiles = (HW + BK - 1) / BK;
-  a.nsplit = bwd_nsplit(a.nrb * B, ntiles);
+  const BwdSplit sp = bwd_split(B, HW);
   // the split sum writes 16-byte rows; without a workspace run unsplit
-  const size_t need = (size_t)a.nsplit * B * HW * BD * sizeof(float);
-  if (a.nsplit > 1 && (!ws || ws_bytes < need || !al16(ws) || ((uintptr_t)out & 15) || ld_out % 8))
-    a.nsplit = 1;
+  const bool split = sp.nsplit > 1 && ws && ws_bytes >= sp.bytes && !misaligned(ws) && !misaligned(out) && ld_out % 8 == 0;
+  a.nsplit = split ? sp.nsplit : 1;
   a.tps = (ntiles + a.nsplit - 1) / a.nsplit;
   a.part = (float*)ws;
   a.nwork = a.nrb * B * a.nsplit;

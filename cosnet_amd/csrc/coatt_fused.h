@@ -1,5 +1,6 @@
 // Shared by the flash co-attention forward / PV kernels (coatt_fused.hip, coatt_dsplit.hip):
-// tile geometry and the launch arguments (rgbd_segmentation_RAA.py:160-170, :213-221).
+// tile geometry and the launch arguments; the padding and key-split rules also serve
+// coatt_flash.hip and coatt_f8.hip (rgbd_segmentation_RAA.py:160-170, :213-221).
 #pragma once
 #include "common.h"
 
@@ -38,6 +39,18 @@ struct FusedArgs {
   int ntiles, smax;
   int* cnt;
 };
+
+// row statistics (lse, klse) are padded to whole 32-key tiles
+static inline int hw_pad32(int HW) { return (HW + 31) / 32 * 32; }
+
+// Key splits for `idle` work items that would leave CUs idle at one workgroup per CU (idle < 256):
+// 256 / idle splits, at most 8, each of at least 16 key tiles.  1: unsplit.
+static inline int key_splits(int idle, int ntiles) {
+  int s = 256 / idle;
+  if (s > 8) s = 8;
+  while (s > 1 && ntiles / s < 16) --s;
+  return s;
+}
 
 // coatt_dsplit.hip: the d-split wave-pair variant (kernel variant 4) of the forward / PV kernel
 int coatt_dsplit_launch(int mode, const FusedArgs& a, dim3 grid, hipStream_t st);

@@ -1021,22 +1021,24 @@ __global__ __launch_bounds__(256) void coatt_merge_k(FusedArgs a) {
 
 }  // namespace
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // Tail split for `items` workgroup-sized work items at one workgroup per CU: the items of the
-// last, partial round of 256 (all of them when there are fewer) are split over up to
-// 256 / tail workgroups each (>= 16 key tiles per split).
+// last, partial round of 256 (all of them when there are fewer) are split by key_splits.
 static void plan_split(int items, int ntiles, int* nfull, int* nsplit) {
-  *nfull = items;
-  *nsplit = 1;
   const int rem = items % 256;   // the partial round (all of it when items < 256)
-  if (rem == 0) return;
-  int s = 256 / rem;
-  if (s > 8) s = 8;
-  while (s > 1 && ntiles / s < 16) --s;
-  if (s < 2) return;
-  *nfull = items - rem;
-  *nsplit = s;
+  *nsplit = rem ? key_splits(rem, ntiles) : 1;
+  *nfull = *nsplit > 1 ? items - rem : items;
+}
+
+// The tail split's partials: un-normalised O [nsplit][tail items][128][ocols] and, for the
+// forward (ocols = FD + 2), each row's (max, sum) after all of O; the PV kernel (ocols = FD)
+// keeps none.  Sizes and carves the workspace; `fits` is false when ws cannot hold it.
+struct TailWs { float *opart, *mlpart; size_t bytes; bool fits; };
+static TailWs tail_layout(int nsplit, int tail_items, int ocols, void* ws, size_t ws_bytes) {
+  const size_t rows = (size_t)nsplit * tail_items * FBQ;
+  TailWs l = {(float*)ws, nullptr, rows * ocols * sizeof(float), false};
+  l.fits = ws && ws_bytes >= l.bytes && !misaligned(ws);
+  if (l.fits && ocols > FD) l.mlpart = l.opart + rows * FD;
+  return l;
 }
 
 // Kernel variant: 1 = coatt_fused_fwd_k (4 waves, one per SIMD, 32 rows per wave), 2 =
@@ -1106,8 +1108,7 @@ extern "C" size_t cn_coatt_fused_workspace_bytes(int B, int HW, int ndir) {
   const int nrb = (HW + FBQ - 1) / FBQ;
   int nfull, s;
   plan_split(nrb * B * ndir, (HW + FBK - 1) / FBK, &nfull, &s);
-  if (s == 1) return 0;
-  return (size_t)s * (nrb * B * ndir - nfull) * FBQ * (FD + 2) * sizeof(float);
+  return s == 1 ? 0 : tail_layout(s, nrb * B * ndir - nfull, FD + 2, nullptr, 0).bytes;
 }
 
 static int fused_check(const void* q, long long ldq, const void* k, long long ldk, const void* v,
@@ -1115,7 +1116,7 @@ static int fused_check(const void* q, long long ldq, const void* k, long long ld
   if (C != FD) return CN_ERR_SHAPE;
   if (ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || ldq < C || ldk < C || ldv < C || ldo < C)
     return CN_ERR_ALIGN;
-  if (!aligned16(q) || !aligned16(k) || !aligned16(v)) return CN_ERR_ALIGN;
+  if (misaligned(q) || misaligned(k) || misaligned(v)) return CN_ERR_ALIGN;
   return 0;
 }
 
@@ -1132,7 +1133,7 @@ static int fused_fwd(const void* vat, long long ld_vat, const void* va, long lon
   if ((ia || ib) && coatt_variant() != 5 && coatt_variant() != 1) return CN_ERR_UNSUPPORTED;
   int rc = fused_check(vat, ld_vat, vb, ld_vb, va, ld_va, ld_z, C);
   if (rc) return rc;
-  if (((uintptr_t)za & 7) || ((uintptr_t)zb & 7)) return CN_ERR_ALIGN;
+  if (misaligned(za, 8) || misaligned(zb, 8)) return CN_ERR_ALIGN;
   FusedArgs a = {};
   int nd = 0;
   // direction 0: Z_a = softmax_j(S) Vb  (queries i: Va_t; keys j: Vb; values Vb)
@@ -1141,21 +1142,17 @@ static int fused_fwd(const void* vat, long long ld_vat, const void* va, long lon
   if (zb) a.dir[nd++] = FusedDir{(const bf16*)vb, (const bf16*)vat, (const bf16*)va, (bf16*)zb, ld_vb, ld_vat, ld_va, ld_z, lse_b, nullptr, ib, ia};
   if (nd == 0) return CN_ERR_SHAPE;
   a.HW = HW;
-  a.HWp = (HW + 31) / 32 * 32;
+  a.HWp = hw_pad32(HW);
   // the merge writes 16-byte rows: unsplit when the outputs are not laid out for that
-  const bool merge_ok = !(((uintptr_t)za & 15) || ((uintptr_t)zb & 15) || (ld_z % 8));
+  const bool merge_ok = !(misaligned(za) || misaligned(zb) || (ld_z % 8));
   if (coatt_variant() == 5) return coatt_q48_launch(0, a, B, nd, merge_ok, ws, ws_bytes, st);
   const int nrb = (HW + FBQ - 1) / FBQ;
   plan_split(nrb * B * nd, (HW + FBK - 1) / FBK, &a.nfull, &a.nsplit);
   if (!merge_ok) a.nsplit = 1;
   if (a.nsplit > 1) {
-    const size_t tail_rows = (size_t)a.nsplit * (nrb * B * nd - a.nfull) * FBQ;
-    if (!ws || ws_bytes < tail_rows * (FD + 2) * sizeof(float) || !aligned16(ws)) {
-      a.nsplit = 1;
-    } else {
-      a.opart = (float*)ws;
-      a.mlpart = a.opart + tail_rows * FD;
-    }
+    const TailWs l = tail_layout(a.nsplit, nrb * B * nd - a.nfull, FD + 2, ws, ws_bytes);
+    if (l.fits) { a.opart = l.opart; a.mlpart = l.mlpart; }
+    else a.nsplit = 1;
   }
   return fused_launch(0, a, B, nd, st);
 }
@@ -1180,7 +1177,7 @@ extern "C" int cn_coatt_fused_fwd_idx(const void* vat, long long ld_vat, const v
                                       const void* vb, long long ld_vb, const int* ia, const int* ib,
                                       int P, int HW, int C, void* za, void* zb, long long ld_z,
                                       void* ws, size_t ws_bytes, hipStream_t st) {
-  if (((uintptr_t)ia & 3) || ((uintptr_t)ib & 3)) return CN_ERR_ALIGN;
+  if (misaligned(ia, 4) || misaligned(ib, 4)) return CN_ERR_ALIGN;
   return fused_fwd(vat, ld_vat, va, ld_va, vb, ld_vb, P, HW, C, za, zb, ld_z, nullptr, nullptr, ws,
                    ws_bytes, st, ia, ib);
 }
@@ -1210,21 +1207,21 @@ extern "C" int cn_coatt_flash_pv_ws(const void* q, long long ldq, const void* k,
   if (B <= 0 || HW <= 0 || !klse || !o) return CN_ERR_SHAPE;
   int rc = fused_check(q, ldq, k, ldk, v, ldv, ldo, C);
   if (rc) return rc;
-  if (((uintptr_t)o & 7) || ((uintptr_t)klse & 15)) return CN_ERR_ALIGN;
+  if (misaligned(o, 8) || misaligned(klse)) return CN_ERR_ALIGN;
   FusedArgs a = {};
   a.dir[0] = FusedDir{(const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, ldq, ldk, ldv, ldo, nullptr, klse};
   a.HW = HW;
-  a.HWp = (HW + 31) / 32 * 32;
+  a.HWp = hw_pad32(HW);
   a.accumulate = accumulate;
-  const bool merge_ok = !(((uintptr_t)o & 15) || (ldo % 8));
+  const bool merge_ok = !(misaligned(o) || (ldo % 8));
   if (coatt_variant() == 5) return coatt_q48_launch(1, a, B, 1, merge_ok, ws, ws_bytes, st);
   const int nrb = (HW + FBQ - 1) / FBQ;
   plan_split(nrb * B, (HW + FBK - 1) / FBK, &a.nfull, &a.nsplit);
   if (!merge_ok) a.nsplit = 1;
   if (a.nsplit > 1) {
-    const size_t tail_rows = (size_t)a.nsplit * (nrb * B - a.nfull) * FBQ;
-    if (!ws || ws_bytes < tail_rows * FD * sizeof(float) || !aligned16(ws)) a.nsplit = 1;
-    a.opart = (float*)ws;
+    const TailWs l = tail_layout(a.nsplit, nrb * B - a.nfull, FD, ws, ws_bytes);
+    if (!l.fits) a.nsplit = 1;
+    a.opart = l.opart;
   }
   return fused_launch(1, a, B, 1, st);
 }

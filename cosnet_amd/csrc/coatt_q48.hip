@@ -682,7 +682,7 @@ int coatt_q48_launch(int mode, FusedArgs& a, int B, int nd, bool merge_ok, void*
   a.nitems = a.nrb * B * nd;
   a.ntiles = (a.HW + FBK - 1) / FBK;
   const size_t need = coatt_q48_workspace_bytes(a.nitems, a.ntiles);
-  const bool cut = merge_ok && need && ws && ws_bytes >= need && ((uintptr_t)ws & 15) == 0;
+  const bool cut = merge_ok && need && ws && ws_bytes >= need && !misaligned(ws);
   q48_plan(a.nitems, a.ntiles, cut, &a.nwork, &a.smax);
   if (a.nwork != a.nitems) {
     const size_t rows = (size_t)a.nitems * a.smax * RB;

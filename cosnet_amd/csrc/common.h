@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/cosnet_hip.h"
 
 typedef __bf16 bf16;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -116,3 +117,24 @@ __device__ __forceinline__ float warp_max(float v) {
 
 #define CN_CHECK_LAUNCH() \
   do { hipError_t e__ = hipGetLastError(); if (e__ != hipSuccess) return (int)e__; } while (0)
+
+// ---- host launch helpers ----------------------------------------------------------------------
+// One launch per entry point: with_dtype(dtype, [&](auto tag) { using T = tag_t<decltype(tag)>;
+// ... }) runs the body with T = bf16 or float and refuses every other dtype code (fp8 is a matrix
+// operand only; elementwise entries have no kernel for it).
+template <class T> struct TypeTag { using type = T; };
+template <class Tag> using tag_t = typename Tag::type;
+template <class F> static inline int with_dtype(int dtype, F&& f) {
+  if (dtype == DT_BF16) return f(TypeTag<bf16>{});
+  if (dtype == DT_F32) return f(TypeTag<float>{});
+  return CN_ERR_UNSUPPORTED;
+}
+
+// elements per 16-byte chunk of a dtype code (VecOf<T>::N inside a typed body)
+static inline int vec_of(int dtype) {
+  return dtype == DT_BF16 ? 8 : (dtype == DT_FP8 || dtype == DT_FP8_E5M2) ? 16 : 4;
+}
+
+static inline bool misaligned(const void* p, int align = 16) {
+  return ((uintptr_t)p & (uintptr_t)(align - 1)) != 0;
+}

@@ -33,15 +33,9 @@ static ConvGeom make_geom(int N, int H, int W, int C, int OH, int OW, int KH, in
   return g;
 }
 
-static int vec_of(int dtype) {
-  return dtype == DT_BF16 ? 8 : (dtype == DT_FP8 || dtype == DT_FP8_E5M2) ? 16 : 4;
-}
-
-static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
-
 // fp8 operands: rows of whole 16-byte chunks from 16-byte aligned bases
 static bool fp8_operands_ok(int C, long long ld, const void* a, const void* b) {
-  return !(C % 16 || ld % 16 || misaligned16(a) || misaligned16(b));
+  return !(C % 16 || ld % 16 || misaligned(a) || misaligned(b));
 }
 
 static int conv_out(int in, int k, int stride, int pad, int dil) {
@@ -206,7 +200,7 @@ extern "C" int cn_conv_fwd_ws(int dtype, const void* x, long long ldx, int N, in
                               size_t ws_floats, hipStream_t st) {
   int ns, ch;
   const int M = N * OH * OW, K = KH * KW * Cin;
-  if (!ws || misaligned16(ws) || misaligned16(y) || ldy % 8 ||
+  if (!ws || misaligned(ws) || misaligned(y) || ldy % 8 ||
       !fwd_split_plan(dtype, M, Cout, K, &ns, &ch) || ws_floats < (size_t)ns * M * Cout)
     return cn_conv_fwd(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, bias, y, ldy,
                        OH, OW, st);
@@ -257,7 +251,7 @@ extern "C" int cn_conv_dgrad_fp8(const void* dy8, long long lddy, int N, int OH,
                                  void* dx, long long lddx, int H, int W, int accumulate,
                                  const float* dy_state, const float* w_state, hipStream_t st) {
   if (!fp8_operands_ok(Cout, lddy, dy8, wt8)) return CN_ERR_ALIGN;
-  if (lddx % 8 || misaligned16(dx)) return CN_ERR_ALIGN;
+  if (lddx % 8 || misaligned(dx)) return CN_ERR_ALIGN;
   GemmArgs a;
   int la;
   int rc = conv_dgrad_args(dy8, lddy, N, OH, OW, Cout, wt8, Cin, KH, KW, pad, dil, dx, lddx, H, W,
@@ -429,7 +423,7 @@ extern "C" int cn_conv_dgrad(int dtype, const void* dy, long long lddy, int N, i
   // (unless accumulating into an existing gradient).
   if (!accumulate) {
     const int vec = vec_of(dtype);
-    if (lddx < Cin || lddx % vec || Cin % vec || misaligned16(dx)) return CN_ERR_ALIGN;
+    if (lddx < Cin || lddx % vec || Cin % vec || misaligned(dx)) return CN_ERR_ALIGN;
     long long n16 = (long long)N * H * W * Cin / vec;
     long long nb = (n16 + 255) / 256;
     if (lddx == Cin)
@@ -659,11 +653,11 @@ extern "C" int cn_conv_wgrad_grouped_ws(int dtype, int G, const void* const* xs,
   int ns, ch, cfg;
   wgrad_plan(dtype, N, OH, OW, Cout, KH, KW, Cin, &ns, &ch, &cfg, G);
   const long long slab = (long long)a.M * a.N;
-  if (ns <= 1 || !ws || ws_floats < (size_t)G * ns * slab || misaligned16(ws) || slab % 4)
+  if (ns <= 1 || !ws || ws_floats < (size_t)G * ns * slab || misaligned(ws) || slab % 4)
     return cn_conv_wgrad_grouped(dtype, G, xs, ldx, N, H, W, Cin, dys, lddy, OH, OW, Cout, KH, KW,
                                  stride, pad, dil, dws, st);
   for (int g = 0; g < G; ++g)
-    if (misaligned16(dws[g])) return CN_ERR_ALIGN;
+    if (misaligned(dws[g])) return CN_ERR_ALIGN;
   wgrad_group(a, G, xs, dys, dws, ws, ns);
   wgrad_split(a, cfg, ns, ch);
   return wgrad_group_split_run(a, dtype, lb, G, dws, ws, st);
@@ -696,14 +690,14 @@ extern "C" int cn_conv_wgrad_fp8(int G, const void* const* xs8, long long ldx, i
   if (ldx % 16 || lddy % 16) return CN_ERR_ALIGN;
   // a null scale state is reported as an alignment error, like a misaligned operand
   for (int g = 0; g < G; ++g)
-    if (misaligned16(xs8[g]) || misaligned16(dys8[g]) || misaligned16(dws[g]) || !x_states[g] ||
+    if (misaligned(xs8[g]) || misaligned(dys8[g]) || misaligned(dws[g]) || !x_states[g] ||
         !dy_states[g])
       return CN_ERR_ALIGN;
   int ns, ch, cfg;
   wgrad_plan(DT_FP8_E5M2, N, OH, OW, Cout, KH, KW, Cin, &ns, &ch, &cfg, G);
   const long long slab = (long long)a.M * a.N;
   const bool split = ns > 1;
-  if (split && (!ws || ws_floats < (size_t)G * ns * slab || misaligned16(ws) || slab % 4))
+  if (split && (!ws || ws_floats < (size_t)G * ns * slab || misaligned(ws) || slab % 4))
     return CN_ERR_SHAPE;
   wgrad_group(a, G, xs8, dys8, dws, split ? ws : nullptr, ns);
   for (int g = 0; g < G; ++g) {

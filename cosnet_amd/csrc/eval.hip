@@ -94,7 +94,7 @@ __global__ __launch_bounds__(512) void soft_iou_k(const float* __restrict__ x,
 extern "C" int cn_soft_iou(const float* x, const unsigned char* gt, int nframes, long long hw,
                            unsigned char* mask, double* iou, long long* counts, hipStream_t st) {
   if (nframes < 1 || hw < 1) return CN_ERR_SHAPE;
-  if (hw % 4 == 0 && (((uintptr_t)x & 15) || ((uintptr_t)gt & 3) || ((uintptr_t)mask & 3)))
+  if (hw % 4 == 0 && (misaligned(x) || misaligned(gt, 4) || misaligned(mask, 4)))
     return CN_ERR_ALIGN;
   hipLaunchKernelGGL(soft_iou_k, dim3(nframes), dim3(512), 0, st, x, gt, hw, mask, iou, counts);
   CN_CHECK_LAUNCH();

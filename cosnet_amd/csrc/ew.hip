@@ -838,50 +838,50 @@ inline int nblocks(long long n, int per = 256) {
 
 extern "C" int cn_nchw_to_nhwc(int dtype, const float* x, int N, int C, int H, int W, int Cp,
                                void* y, hipStream_t st) {
-  if (Cp % (dtype == DT_BF16 ? 8 : 4) || ((uintptr_t)y & 15)) return CN_ERR_ALIGN;
-  long long n = (long long)N * H * W;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(nchw_to_nhwc_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, x, N, C, H, W, Cp, (bf16*)y);
-  else
-    hipLaunchKernelGGL(nchw_to_nhwc_k<float>, dim3(nblocks(n)), dim3(256), 0, st, x, N, C, H, W, Cp, (float*)y);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (Cp % VecOf<T>::N || misaligned(y)) return CN_ERR_ALIGN;
+    long long n = (long long)N * H * W;
+    hipLaunchKernelGGL(nchw_to_nhwc_k<T>, dim3(nblocks(n)), dim3(256), 0, st, x, N, C, H, W, Cp, (T*)y);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_weight_prep(int dtype, const float* w, int Cout, int KHW, int Cin, int Cp,
                               void* wf, void* wt, hipStream_t st) {
-  long long n = (long long)Cout * KHW * Cp;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(weight_prep_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, w, Cout, KHW, Cin, Cp, (bf16*)wf, (bf16*)wt);
-  else
-    hipLaunchKernelGGL(weight_prep_k<float>, dim3(nblocks(n)), dim3(256), 0, st, w, Cout, KHW, Cin, Cp, (float*)wf, (float*)wt);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    long long n = (long long)Cout * KHW * Cp;
+    hipLaunchKernelGGL(weight_prep_k<T>, dim3(nblocks(n)), dim3(256), 0, st, w, Cout, KHW, Cin, Cp, (T*)wf, (T*)wt);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_maxpool_fwd(int dtype, const void* x, int N, int H, int W, int C, int OH, int OW,
                               int k, int s, int pad, void* y, unsigned char* argmax, hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  long long n = (long long)N * OH * OW * (C / (dtype == DT_BF16 ? 8 : 4));
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(maxpool_fwd_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, (const bf16*)x, N, H, W, C, OH, OW, k, s, pad, (bf16*)y, argmax);
-  else
-    hipLaunchKernelGGL(maxpool_fwd_k<float>, dim3(nblocks(n)), dim3(256), 0, st, (const float*)x, N, H, W, C, OH, OW, k, s, pad, (float*)y, argmax);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % VecOf<T>::N) return CN_ERR_ALIGN;
+    long long n = (long long)N * OH * OW * (C / VecOf<T>::N);
+    hipLaunchKernelGGL(maxpool_fwd_k<T>, dim3(nblocks(n)), dim3(256), 0, st, (const T*)x, N, H, W, C, OH, OW, k, s, pad, (T*)y, argmax);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_maxpool_bwd(int dtype, const void* dy, const unsigned char* argmax, int N, int H,
                               int W, int C, int OH, int OW, int k, int s, int pad, void* dx,
                               hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  long long n = (long long)N * H * W * (C / (dtype == DT_BF16 ? 8 : 4));
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(maxpool_bwd_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, (const bf16*)dy, argmax, N, H, W, C, OH, OW, k, s, pad, (bf16*)dx);
-  else
-    hipLaunchKernelGGL(maxpool_bwd_k<float>, dim3(nblocks(n)), dim3(256), 0, st, (const float*)dy, argmax, N, H, W, C, OH, OW, k, s, pad, (float*)dx);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % VecOf<T>::N) return CN_ERR_ALIGN;
+    long long n = (long long)N * H * W * (C / VecOf<T>::N);
+    hipLaunchKernelGGL(maxpool_bwd_k<T>, dim3(nblocks(n)), dim3(256), 0, st, (const T*)dy, argmax, N, H, W, C, OH, OW, k, s, pad, (T*)dx);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 static int avgpool_splits(int N, int HW, int C, int V) {
@@ -892,79 +892,78 @@ static int avgpool_splits(int N, int HW, int C, int V) {
 }
 
 extern "C" size_t cn_avgpool_workspace_floats(int dtype, int N, int HW, int C) {
-  return (size_t)avgpool_splits(N, HW, C, dtype == DT_BF16 ? 8 : 4) * N * C;
+  return (size_t)avgpool_splits(N, HW, C, vec_of(dtype)) * N * C;
 }
 
 extern "C" int cn_avgpool(int dtype, const void* x, long long ld, int N, int HW, int C,
                           float scale, void* y, float* ws, hipStream_t st) {
-  int V = dtype == DT_BF16 ? 8 : 4;
-  if (C % V) return CN_ERR_ALIGN;
-  int gx = (C / V + 63) / 64;
-  int rs = avgpool_splits(N, HW, C, V);
-  dim3 grid(gx, N, rs);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(avgpool_partial_k<bf16>, grid, dim3(256), 0, st, (const bf16*)x, ld, HW, C, ws);
-  else
-    hipLaunchKernelGGL(avgpool_partial_k<float>, grid, dim3(256), 0, st, (const float*)x, ld, HW, C, ws);
-  CN_CHECK_LAUNCH();
-  long long n = (long long)N * C;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(avgpool_final_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, ws, rs, n, scale, (bf16*)y);
-  else
-    hipLaunchKernelGGL(avgpool_final_k<float>, dim3(nblocks(n)), dim3(256), 0, st, ws, rs, n, scale, (float*)y);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int V = VecOf<T>::N;
+    if (C % V) return CN_ERR_ALIGN;
+    int gx = (C / V + 63) / 64;
+    int rs = avgpool_splits(N, HW, C, V);
+    hipLaunchKernelGGL(avgpool_partial_k<T>, dim3(gx, N, rs), dim3(256), 0, st, (const T*)x, ld, HW, C, ws);
+    CN_CHECK_LAUNCH();
+    long long n = (long long)N * C;
+    hipLaunchKernelGGL(avgpool_final_k<T>, dim3(nblocks(n)), dim3(256), 0, st, ws, rs, n, scale, (T*)y);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_bcast_rows(int dtype, const void* src, int N, int HW, int C, float scale,
                              void* dst, long long ld, int accumulate, hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  long long n = (long long)N * HW * (C / (dtype == DT_BF16 ? 8 : 4));
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(bcast_rows_k<bf16>, dim3(nblocks(n)), dim3(256), 0, st, (const bf16*)src, N, HW, C, scale, (bf16*)dst, ld, accumulate);
-  else
-    hipLaunchKernelGGL(bcast_rows_k<float>, dim3(nblocks(n)), dim3(256), 0, st, (const float*)src, N, HW, C, scale, (float*)dst, ld, accumulate);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % VecOf<T>::N) return CN_ERR_ALIGN;
+    long long n = (long long)N * HW * (C / VecOf<T>::N);
+    hipLaunchKernelGGL(bcast_rows_k<T>, dim3(nblocks(n)), dim3(256), 0, st, (const T*)src, N, HW, C, scale, (T*)dst, ld, accumulate);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_gate_fwd(int dtype, const void* z, long long ldz, int P, int C, const float* g,
                            const float* gb, void* out, long long ldo, float* mask, hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  dim3 grid((P + 3) / 4);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(gate_fwd_k<bf16>, grid, dim3(256), 0, st, (const bf16*)z, ldz, P, C, g, gb, (bf16*)out, ldo, mask);
-  else
-    hipLaunchKernelGGL(gate_fwd_k<float>, grid, dim3(256), 0, st, (const float*)z, ldz, P, C, g, gb, (float*)out, ldo, mask);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % VecOf<T>::N) return CN_ERR_ALIGN;
+    hipLaunchKernelGGL(gate_fwd_k<T>, dim3((P + 3) / 4), dim3(256), 0, st, (const T*)z, ldz, P, C, g, gb, (T*)out, ldo, mask);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_gate_cat_idx(int dtype, const void* z, long long ldz, const void* vbank,
                                long long ldv, const int* iv, int P, int HW, int C, const float* g,
                                const float* gb, void* out, long long ldo, hipStream_t st) {
-  if (dtype != DT_BF16 && dtype != DT_F32) return CN_ERR_UNSUPPORTED;
-  if (P <= 0 || HW <= 0 || C <= 0 || ldz < C || ldv < C || ldo < 2 * C) return CN_ERR_SHAPE;
-  const int V = dtype == DT_BF16 ? 8 : 4;
-  if (C % V || ldz % V || ldv % V || ldo % V) return CN_ERR_ALIGN;
-  if (((uintptr_t)z & 15) || ((uintptr_t)vbank & 15) || ((uintptr_t)out & 15) || ((uintptr_t)iv & 3))
-    return CN_ERR_ALIGN;
-  if (C / V > 64) return CN_ERR_UNSUPPORTED;   // one chunk per lane
-  const long long rows = (long long)P * HW;
-  if (rows > 0x7fffffffll) return CN_ERR_SHAPE;
-  const dim3 grid((unsigned)((rows + 3) / 4));
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(gate_cat_idx_k<bf16>, grid, dim3(256), 0, st, (const bf16*)z, ldz, (const bf16*)vbank, ldv, iv, P, HW, C, g, gb, (bf16*)out, ldo);
-  else
-    hipLaunchKernelGGL(gate_cat_idx_k<float>, grid, dim3(256), 0, st, (const float*)z, ldz, (const float*)vbank, ldv, iv, P, HW, C, g, gb, (float*)out, ldo);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int V = VecOf<T>::N;
+    if (P <= 0 || HW <= 0 || C <= 0 || ldz < C || ldv < C || ldo < 2 * C) return CN_ERR_SHAPE;
+    if (C % V || ldz % V || ldv % V || ldo % V) return CN_ERR_ALIGN;
+    if (misaligned(z) || misaligned(vbank) || misaligned(out) || misaligned(iv, 4)) return CN_ERR_ALIGN;
+    if (C / V > 64) return CN_ERR_UNSUPPORTED;   // one chunk per lane
+    const long long rows = (long long)P * HW;
+    if (rows > 0x7fffffffll) return CN_ERR_SHAPE;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    hipLaunchKernelGGL(gate_cat_idx_k<T>, grid, dim3(256), 0, st, (const T*)z, ldz, (const T*)vbank, ldv, iv, P, HW, C, g, gb, (T*)out, ldo);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
-static int rowpart_blocks(int P) { return nblocks(P, 4 * 16); }
+// Column-partial workspace of cn_gate_bwd / cn_head_bwd / cn_colsum: [nb][C] row-block partials of
+// the column sums, then [nb] partials of the scalar sum (gate / head backward only).
+struct ColPart { int nb; float *cols, *scalar; size_t floats; };
+static ColPart colpart_layout(int P, int C, float* ws) {
+  const int nb = nblocks(P, 4 * 16);
+  return {nb, ws, ws + (long long)nb * C, (size_t)nb * (size_t)(C + 1)};
+}
 
 extern "C" size_t cn_colpart_workspace_floats(int P, int C) {
-  return (size_t)rowpart_blocks(P) * (size_t)(C + 1);
+  return colpart_layout(P, C, nullptr).floats;
 }
 
 static int colreduce(const float* ws, int nb, int C, float* out, hipStream_t st) {
@@ -1051,52 +1050,53 @@ extern "C" int cn_gate_bwd(int dtype, const void* z, long long ldz, const void* 
                            const float* mask, int P, int C, const float* g, int through_mask,
                            void* dz, long long lddz, float* dg, float* dgb, float* ws,
                            hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  if (C / (dtype == DT_BF16 ? 8 : 4) > 64) return CN_ERR_UNSUPPORTED;
-  if ((dg || dgb) && !ws) return CN_ERR_SHAPE;
-  int nb = rowpart_blocks(P);
-  float* w = (dg || dgb) ? ws : nullptr;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(gate_bwd_k<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)z, ldz, (const bf16*)dout, lddo, mask, P, C, g, through_mask, (bf16*)dz, lddz, w);
-  else
-    hipLaunchKernelGGL(gate_bwd_k<float>, dim3(nb), dim3(256), 0, st, (const float*)z, ldz, (const float*)dout, lddo, mask, P, C, g, through_mask, (float*)dz, lddz, w);
-  CN_CHECK_LAUNCH();
-  if (!w) return 0;
-  int rc = colreduce(ws, nb, C, dg, st);
-  if (rc) return rc;
-  return colreduce(ws + (long long)nb * C, nb, 1, dgb, st);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int V = VecOf<T>::N;
+    if (C % V) return CN_ERR_ALIGN;
+    if (C / V > 64) return CN_ERR_UNSUPPORTED;
+    if ((dg || dgb) && !ws) return CN_ERR_SHAPE;
+    const ColPart l = colpart_layout(P, C, ws);
+    float* w = (dg || dgb) ? l.cols : nullptr;
+    hipLaunchKernelGGL(gate_bwd_k<T>, dim3(l.nb), dim3(256), 0, st, (const T*)z, ldz, (const T*)dout, lddo, mask, P, C, g, through_mask, (T*)dz, lddz, w);
+    CN_CHECK_LAUNCH();
+    if (!w) return 0;
+    int rc = colreduce(l.cols, l.nb, C, dg, st);
+    if (rc) return rc;
+    return colreduce(l.scalar, l.nb, 1, dgb, st);
+  });
 }
 
 extern "C" int cn_head_fwd(int dtype, const void* a, long long lda, const void* b, long long ldb,
                            int P, int C, int relu, const float* w, const float* bias, void* zout,
                            long long ldz, float* logit, hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  dim3 grid((P + 3) / 4);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(head_fwd_k<bf16>, grid, dim3(256), 0, st, (const bf16*)a, lda, (const bf16*)b, ldb, P, C, relu, w, bias, (bf16*)zout, ldz, logit);
-  else
-    hipLaunchKernelGGL(head_fwd_k<float>, grid, dim3(256), 0, st, (const float*)a, lda, (const float*)b, ldb, P, C, relu, w, bias, (float*)zout, ldz, logit);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % VecOf<T>::N) return CN_ERR_ALIGN;
+    hipLaunchKernelGGL(head_fwd_k<T>, dim3((P + 3) / 4), dim3(256), 0, st, (const T*)a, lda, (const T*)b, ldb, P, C, relu, w, bias, (T*)zout, ldz, logit);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_head_bwd(int dtype, const void* z, long long ldz, const float* dlogit, int P, int C,
                            int relu, const float* w, void* dz, long long lddz, float* dw, float* db,
                            float* ws, hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  if (C / (dtype == DT_BF16 ? 8 : 4) > 64) return CN_ERR_UNSUPPORTED;
-  if ((dw || db) && !ws) return CN_ERR_SHAPE;
-  int nb = rowpart_blocks(P);
-  float* wp = (dw || db) ? ws : nullptr;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(head_bwd_k<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)z, ldz, dlogit, P, C, relu, w, (bf16*)dz, lddz, wp);
-  else
-    hipLaunchKernelGGL(head_bwd_k<float>, dim3(nb), dim3(256), 0, st, (const float*)z, ldz, dlogit, P, C, relu, w, (float*)dz, lddz, wp);
-  CN_CHECK_LAUNCH();
-  if (!wp) return 0;
-  int rc = colreduce(ws, nb, C, dw, st);
-  if (rc) return rc;
-  return colreduce(ws + (long long)nb * C, nb, 1, db, st);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int V = VecOf<T>::N;
+    if (C % V) return CN_ERR_ALIGN;
+    if (C / V > 64) return CN_ERR_UNSUPPORTED;
+    if ((dw || db) && !ws) return CN_ERR_SHAPE;
+    const ColPart l = colpart_layout(P, C, ws);
+    float* wp = (dw || db) ? l.cols : nullptr;
+    hipLaunchKernelGGL(head_bwd_k<T>, dim3(l.nb), dim3(256), 0, st, (const T*)z, ldz, dlogit, P, C, relu, w, (T*)dz, lddz, wp);
+    CN_CHECK_LAUNCH();
+    if (!wp) return 0;
+    int rc = colreduce(l.cols, l.nb, C, dw, st);
+    if (rc) return rc;
+    return colreduce(l.scalar, l.nb, 1, db, st);
+  });
 }
 
 extern "C" int cn_upsample_sigmoid(const float* in, int N, int h, int w, int H, int W,
@@ -1161,15 +1161,14 @@ extern "C" int cn_sgd(const void* tensors, int nt, const float* lrs, float wd, f
 
 extern "C" int cn_rowdot_seg(int dtype, const void* a, long long lda, const void* b, long long ldb,
                              int P, int C, int seg, int seg_ld, float* out, hipStream_t st) {
-  if (C % (dtype == DT_BF16 ? 8 : 4)) return CN_ERR_ALIGN;
-  if (seg < 1 || seg_ld < seg) return CN_ERR_SHAPE;
-  dim3 grid((P + 3) / 4);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(rowdot_k<bf16>, grid, dim3(256), 0, st, (const bf16*)a, lda, (const bf16*)b, ldb, P, C, seg, seg_ld, out);
-  else
-    hipLaunchKernelGGL(rowdot_k<float>, grid, dim3(256), 0, st, (const float*)a, lda, (const float*)b, ldb, P, C, seg, seg_ld, out);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % VecOf<T>::N) return CN_ERR_ALIGN;
+    if (seg < 1 || seg_ld < seg) return CN_ERR_SHAPE;
+    hipLaunchKernelGGL(rowdot_k<T>, dim3((P + 3) / 4), dim3(256), 0, st, (const T*)a, lda, (const T*)b, ldb, P, C, seg, seg_ld, out);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" int cn_rowdot(int dtype, const void* a, long long lda, const void* b, long long ldb,
@@ -1179,31 +1178,31 @@ extern "C" int cn_rowdot(int dtype, const void* a, long long lda, const void* b,
 
 extern "C" int cn_colsum(int dtype, const void* x, long long ld, int P, int C, float* out, float* ws,
                          hipStream_t st) {
-  int V = dtype == DT_BF16 ? 8 : 4;
-  if (C % V) return CN_ERR_ALIGN;
-  int gx = (C / V + 63) / 64;
-  int gy = (P + 63) / 64;
-  if (gy > 256) gy = 256;
-  if (gy > rowpart_blocks(P)) gy = rowpart_blocks(P);  // fits cn_colpart_workspace_floats
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(colsum_k<bf16>, dim3(gx, gy), dim3(256), 0, st, (const bf16*)x, ld, P, C, ws);
-  else
-    hipLaunchKernelGGL(colsum_k<float>, dim3(gx, gy), dim3(256), 0, st, (const float*)x, ld, P, C, ws);
-  CN_CHECK_LAUNCH();
-  return colreduce(ws, gy, C, out, st);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int V = VecOf<T>::N;
+    if (C % V) return CN_ERR_ALIGN;
+    const ColPart l = colpart_layout(P, C, ws);
+    int gx = (C / V + 63) / 64;
+    int gy = (P + 63) / 64;
+    if (gy > 256) gy = 256;
+    if (gy > l.nb) gy = l.nb;  // the partial rows fit the layout's [nb][C]
+    hipLaunchKernelGGL(colsum_k<T>, dim3(gx, gy), dim3(256), 0, st, (const T*)x, ld, P, C, l.cols);
+    CN_CHECK_LAUNCH();
+    return colreduce(l.cols, gy, C, out, st);
+  });
 }
 
 extern "C" int cn_cast2d(int dtype_in, int dtype_out, const void* x, long long ldx, int P, int C,
                          void* y, long long ldy, int accumulate, hipStream_t st) {
-  int nb = nblocks((long long)P * C);
-  if (dtype_in == DT_F32 && dtype_out == DT_BF16)
-    hipLaunchKernelGGL((cast2d_k<float, bf16>), dim3(nb), dim3(256), 0, st, (const float*)x, ldx, P, C, (bf16*)y, ldy, accumulate);
-  else if (dtype_in == DT_BF16 && dtype_out == DT_F32)
-    hipLaunchKernelGGL((cast2d_k<bf16, float>), dim3(nb), dim3(256), 0, st, (const bf16*)x, ldx, P, C, (float*)y, ldy, accumulate);
-  else if (dtype_in == DT_F32)
-    hipLaunchKernelGGL((cast2d_k<float, float>), dim3(nb), dim3(256), 0, st, (const float*)x, ldx, P, C, (float*)y, ldy, accumulate);
-  else
-    hipLaunchKernelGGL((cast2d_k<bf16, bf16>), dim3(nb), dim3(256), 0, st, (const bf16*)x, ldx, P, C, (bf16*)y, ldy, accumulate);
-  CN_CHECK_LAUNCH();
-  return 0;
+  return with_dtype(dtype_in, [&](auto tin) {
+    return with_dtype(dtype_out, [&](auto tout) {
+      using TI = tag_t<decltype(tin)>;
+      using TO = tag_t<decltype(tout)>;
+      int nb = nblocks((long long)P * C);
+      hipLaunchKernelGGL((cast2d_k<TI, TO>), dim3(nb), dim3(256), 0, st, (const TI*)x, ldx, P, C, (TO*)y, ldy, accumulate);
+      CN_CHECK_LAUNCH();
+      return 0;
+    });
+  });
 }

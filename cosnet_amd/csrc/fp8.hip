@@ -167,45 +167,41 @@ __global__ void fp8_update_list_k(const Fp8Rec* __restrict__ recs, int n, float 
 
 extern "C" int cn_fp8_quant_fmt(int dtype, int fmt, const void* x, long long ldx, int P, int C,
                                 void* y8, long long ldy, float* state, int mode, hipStream_t st) {
-  if (C % 8 || ldx % 8 || ldy % 8 || !state) return CN_ERR_ALIGN;
-  if (fmt != 0 && fmt != 1) return CN_ERR_UNSUPPORTED;
-  if (P <= 0) return 0;
-  const int gx = (C / 8 + 63) / 64;
-  int gy = (P + 63) / 64;                      // >= 16 rows per thread
-  const int maxy = (1024 + gx - 1) / gx;       // ~1024 blocks: 4 per CU
-  if (gy > maxy) gy = maxy;
-  if (gy < 1) gy = 1;
-  const dim3 grid(gx, gy);
-  auto launch = [&](int quantise, int collect) {
-    if (dtype == DT_BF16 && fmt == 0)
-      hipLaunchKernelGGL((quant_fp8_k<bf16, 0>), grid, dim3(256), 0, st, (const bf16*)x, ldx, P, C,
-                         (unsigned char*)y8, ldy, state, quantise, collect);
-    else if (dtype == DT_BF16)
-      hipLaunchKernelGGL((quant_fp8_k<bf16, 1>), grid, dim3(256), 0, st, (const bf16*)x, ldx, P, C,
-                         (unsigned char*)y8, ldy, state, quantise, collect);
-    else if (fmt == 0)
-      hipLaunchKernelGGL((quant_fp8_k<float, 0>), grid, dim3(256), 0, st, (const float*)x, ldx, P, C,
-                         (unsigned char*)y8, ldy, state, quantise, collect);
-    else
-      hipLaunchKernelGGL((quant_fp8_k<float, 1>), grid, dim3(256), 0, st, (const float*)x, ldx, P, C,
-                         (unsigned char*)y8, ldy, state, quantise, collect);
-  };
-  if (dtype != DT_BF16 && dtype != DT_F32) return CN_ERR_UNSUPPORTED;
-  if (mode == 0) {          // delayed: quantise with the current scale, collect this amax
-    launch(1, 1);
-  } else if (mode == 1) {   // current: amax pass, scale update, quantise
-    launch(0, 1);
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % 8 || ldx % 8 || ldy % 8 || !state) return CN_ERR_ALIGN;
+    if (fmt != 0 && fmt != 1) return CN_ERR_UNSUPPORTED;
+    if (P <= 0) return 0;
+    const int gx = (C / 8 + 63) / 64;
+    int gy = (P + 63) / 64;                      // >= 16 rows per thread
+    const int maxy = (1024 + gx - 1) / gx;       // ~1024 blocks: 4 per CU
+    if (gy > maxy) gy = maxy;
+    if (gy < 1) gy = 1;
+    const dim3 grid(gx, gy);
+    auto launch = [&](int quantise, int collect) {
+      if (fmt == 0)
+        hipLaunchKernelGGL((quant_fp8_k<T, 0>), grid, dim3(256), 0, st, (const T*)x, ldx, P, C,
+                           (unsigned char*)y8, ldy, state, quantise, collect);
+      else
+        hipLaunchKernelGGL((quant_fp8_k<T, 1>), grid, dim3(256), 0, st, (const T*)x, ldx, P, C,
+                           (unsigned char*)y8, ldy, state, quantise, collect);
+    };
+    if (mode == 0) {          // delayed: quantise with the current scale, collect this amax
+      launch(1, 1);
+    } else if (mode == 1) {   // current: amax pass, scale update, quantise
+      launch(0, 1);
+      CN_CHECK_LAUNCH();
+      hipLaunchKernelGGL(fp8_update_k, dim3(1), dim3(64), 0, st, state, 1, 1.f);
+      CN_CHECK_LAUNCH();
+      launch(1, 0);
+    } else if (mode == 2) {   // amax only (calibration of a delayed-scaling state)
+      launch(0, 1);
+    } else {
+      return CN_ERR_SHAPE;
+    }
     CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fp8_update_k, dim3(1), dim3(64), 0, st, state, 1, 1.f);
-    CN_CHECK_LAUNCH();
-    launch(1, 0);
-  } else if (mode == 2) {   // amax only (calibration of a delayed-scaling state)
-    launch(0, 1);
-  } else {
-    return CN_ERR_SHAPE;
-  }
-  CN_CHECK_LAUNCH();
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int cn_fp8_quant(int dtype, const void* x, long long ldx, int P, int C, void* y8,
