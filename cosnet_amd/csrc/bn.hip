@@ -456,6 +456,95 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
   if (y8) fp8_block_amax(qmax, qstate);
 }
 
+// ---- static-scale apply (inference, cosnet_amd/fp8_infer.py) --------------------------------
+// bn_apply_k's arithmetic with the e4m3 image of the fp32 activation written under a FROZEN
+// scale: qstate is only read, so there is no amax, no atomic and no block-wide reduction, and the
+// threads past the chunk columns / row groups simply leave (bn_apply_k keeps them for its one
+// reduction).  y is optional: an activation that only fp8 convs read exists as bytes alone.
+template <class T>
+__global__ __launch_bounds__(256) void bn_apply_q8_k(const T* __restrict__ x, long long ldx, int P, int C,
+                                                     const float* mean, const float* invstd,
+                                                     const float* gamma, const float* beta,
+                                                     const T* __restrict__ res, long long ldr,
+                                                     const T* __restrict__ xr, long long ldxr,
+                                                     const float* rmean, const float* rinvstd,
+                                                     const float* rgamma, const float* rbeta, int act,
+                                                     const float* prelu, T* __restrict__ y,
+                                                     long long ldy, unsigned char* __restrict__ y8,
+                                                     long long ldy8, const float* __restrict__ qstate,
+                                                     int wt) {
+  constexpr int V = VecOf<T>::N;
+  static_assert(V == 8, "the e4m3 image is packed from 8-channel chunks (bf16)");
+  const __amdgpu_buffer_rsrc_t yrs = wt_rsrc(y);
+  const Layout L = layout_of<T>(C);
+  const int tx = threadIdx.x % L.CB, ty = threadIdx.x / L.CB;
+  const int chunk = blockIdx.x * L.CB + tx;
+  if (chunk >= L.CPR || ty >= L.RPB) return;
+  const float qinv = qstate[1];
+  const int seg = blockIdx.z, c0 = chunk * V;
+  const long long row0 = (long long)seg * P;
+  float sc[V], sf[V], rsc[V], rsf[V], t0[V], t1[V];
+  ld_params<V>(gamma, c0, 1.f, sc);
+  ld_params<V>(beta, c0, 0.f, sf);
+  ld_params<V>(invstd + seg * C, c0, 1.f, t0);
+  ld_params<V>(mean + seg * C, c0, 0.f, t1);
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    sc[v] *= t0[v];
+    sf[v] -= t1[v] * sc[v];
+  }
+  if (xr) {
+    ld_params<V>(rgamma, c0, 1.f, rsc);
+    ld_params<V>(rbeta, c0, 0.f, rsf);
+    ld_params<V>(rinvstd + seg * C, c0, 1.f, t0);
+    ld_params<V>(rmean + seg * C, c0, 0.f, t1);
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      rsc[v] *= t0[v];
+      rsf[v] -= t1[v] * rsc[v];
+    }
+  }
+  const float a = (act == 2) ? prelu[0] : 0.f;
+  const int step = gridDim.y * L.RPB;
+  for (int r0 = blockIdx.y * L.RPB + ty; r0 < P; r0 += UNR * step) {
+    float f[UNR][V], q[UNR][V];
+    // loads as in bn_apply_k: rows past P re-read the segment's first row and are not stored
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const long long r = row0 + (r0 + u * step < P ? r0 + u * step : 0);
+      ld_chunk(x + r * ldx + c0, f[u]);
+      if (res) ld_chunk(res + r * ldr + c0, q[u]);
+      if (xr) ld_chunk(xr + r * ldxr + c0, q[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const long long r = row0 + r0 + u * step;
+      if (r0 + u * step >= P) break;
+#pragma unroll
+      for (int v = 0; v < V; ++v) {
+        float t = fmaf(f[u][v], sc[v], sf[v]);
+        if (res) t += q[u][v];
+        if (xr) t += fmaf(q[u][v], rsc[v], rsf[v]);
+        if (act == 1) t = fmaxf(t, 0.f);
+        else if (act == 2) t = t > 0.f ? t : a * t;
+        f[u][v] = t;
+      }
+      if (y) {
+        const u32x4 pk = Chunk<T>::pack(f[u]);
+        if (wt)
+          __builtin_amdgcn_raw_buffer_store_b128(pk, yrs, (int)((r * ldy + c0) * (long long)sizeof(T)), 0, 16);
+        else
+          *(u32x4*)(y + r * ldy + c0) = pk;
+      }
+      // the bytes of the fp32 value before its rounding to bf16, as bn_apply_k writes them
+      u32x2 o;
+      o.x = pack4_fp8_bn(f[u][0] * qinv, f[u][1] * qinv, f[u][2] * qinv, f[u][3] * qinv);
+      o.y = pack4_fp8_bn(f[u][4] * qinv, f[u][5] * qinv, f[u][6] * qinv, f[u][7] * qinv);
+      *(u32x2*)(y8 + r * ldy8 + c0) = o;
+    }
+  }
+}
+
 // ---- backward reduce: planes sum(dz), sum(dz * xhat) [, sum(dz * pre * (pre<=0)) PReLU] ----
 // dz = dy * mask, mask = (y > 0) for act 1, 1 for act 0, (pre > 0 ? 1 : a) for act 2.
 // act 4: the ReLU mask comes as bits (bn_apply_k's mask output): mk[row * ldm + chunk], bit v.
@@ -842,6 +931,41 @@ extern "C" int cn_bn_apply_ex(int dtype, const void* x, long long ldx, int P, in
                        ldm, wt);
     CN_CHECK_LAUNCH();
     return 0;
+  });
+}
+
+// Inference with frozen fp8 scales: the eval-mode apply whose e4m3 image y8 is written under
+// the read-only qstate; y (bf16) only when given.  bf16 only, like the fp8 copy of cn_bn_apply_ex.
+extern "C" int cn_bn_apply_q8(int dtype, const void* x, long long ldx, int P, int nseg, int C,
+                              const float* mean, const float* invstd, const float* gamma,
+                              const float* beta, const void* res, long long ldr, const void* xr,
+                              long long ldxr, const float* rmean, const float* rinvstd,
+                              const float* rgamma, const float* rbeta, int act, const float* prelu,
+                              void* y, long long ldy, void* y8, long long ldy8, const float* qstate,
+                              hipStream_t st) {
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    constexpr int vec = VecOf<T>::N;
+    if constexpr (vec != 8) {
+      return CN_ERR_ALIGN;   // fp32 input: the e4m3 image exists for bf16 only
+    } else {
+      if (!y8 || !qstate || ldy8 % 16 || misaligned(y8, 8)) return CN_ERR_ALIGN;
+      if (C % vec || ldx % vec || (y && ldy % vec) || (res && ldr % vec) || (xr && ldxr % vec))
+        return CN_ERR_ALIGN;
+      if (misaligned(x) || misaligned(y) || misaligned(res) || misaligned(xr)) return CN_ERR_ALIGN;
+      if (misaligned(mean) || misaligned(invstd) || misaligned(gamma) || misaligned(beta) ||
+          misaligned(rmean) || misaligned(rinvstd) || misaligned(rgamma) || misaligned(rbeta))
+        return CN_ERR_ALIGN;
+      if (P < 1 || nseg < 1 || C < vec || ldy8 < C || (act == 2 && !prelu)) return CN_ERR_SHAPE;
+      const int wt = y ? bn_wt((long long)nseg * P, ldy, (int)sizeof(T)) : 0;
+      int gx, gy = grid_rows<T>(P, C, &gx, g_tune[T_AP_ROWS], g_tune[T_AP_BLOCKS], nseg);
+      hipLaunchKernelGGL(bn_apply_q8_k<T>, dim3(gx, gy, nseg), dim3(256), 0, st, (const T*)x, ldx, P, C,
+                         mean, invstd, gamma, beta, (const T*)res, ldr, (const T*)xr, ldxr, rmean,
+                         rinvstd, rgamma, rbeta, act, prelu, (T*)y, ldy, (unsigned char*)y8, ldy8,
+                         qstate, wt);
+      CN_CHECK_LAUNCH();
+      return 0;
+    }
   });
 }
 

@@ -96,6 +96,56 @@ __global__ __launch_bounds__(256) void quant_fp8_k(const T* __restrict__ x, long
   if (collect) wave_amax_atomic(m, state);
 }
 
+// Static scaling (inference, cosnet_amd/fp8_infer.py): quant_fp8_k's quantisation under a FROZEN
+// scale.  The state is only read -- no amax, no atomic, no block-wide reduction -- so the bytes
+// are those of the delayed mode for the same state and nothing here depends on earlier launches.
+template <class T, int FMT>
+__global__ __launch_bounds__(256) void quant_static_k(const T* __restrict__ x, long long ldx, int P, int C,
+                                                      unsigned char* __restrict__ y, long long ldy,
+                                                      const float* __restrict__ state) {
+  const float inv = state[1];
+  const int c = (blockIdx.x * 64 + (threadIdx.x & 63)) * 8;
+  if (c >= C) return;
+  constexpr int U = 4;  // rows in flight per thread
+  const int step = 4 * gridDim.y;
+  for (int r0 = blockIdx.y * 4 + (threadIdx.x >> 6); r0 < P; r0 += U * step) {
+    float f[U][8];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int r = r0 + u * step;
+      if (r >= P) break;
+      if constexpr (sizeof(T) == 2) {
+        Chunk<bf16>::unpack(*(const u32x4*)(x + (long long)r * ldx + c), f[u]);
+      } else {
+        *(f32x4*)&f[u][0] = *(const f32x4*)(x + (long long)r * ldx + c);
+        *(f32x4*)&f[u][4] = *(const f32x4*)(x + (long long)r * ldx + c + 4);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int r = r0 + u * step;
+      if (r >= P) break;
+      u32x2 o;
+      o.x = pack4<FMT>(f[u][0] * inv, f[u][1] * inv, f[u][2] * inv, f[u][3] * inv);
+      o.y = pack4<FMT>(f[u][4] * inv, f[u][5] * inv, f[u][6] * inv, f[u][7] * inv);
+      *(u32x2*)(y + (long long)r * ldy + c) = o;
+    }
+  }
+}
+
+// dst[(n*HW + p)*ldd + c] = src[n*C + c] over bytes, one 16-byte chunk per thread and step (the
+// e4m3 image of the ASPP's pooled rows broadcast into the concat's image)
+__global__ __launch_bounds__(256) void bcast_rows_u8_k(const unsigned char* __restrict__ src, int HW,
+                                                       int C16, long long chunks,
+                                                       unsigned char* __restrict__ dst, long long ldd) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < chunks; i += (long long)gridDim.x * 256) {
+    const long long r = i / C16;
+    const int cc = (int)(i - r * C16);
+    const long long n = r / HW;
+    *(u32x4*)(dst + r * ldd + cc * 16) = *(const u32x4*)(src + (n * C16 + cc) * 16);
+  }
+}
+
 // scale = amax / (fmt max / 2^margin); a zero amax (all-zero tensor) keeps the previous scale.
 // state[3] = the format's max finite value (0: e4m3's 448; 57344 for e5m2 gradient states)
 __global__ void fp8_update_k(float* state, int nstates, float margin) {
@@ -202,6 +252,43 @@ extern "C" int cn_fp8_quant_fmt(int dtype, int fmt, const void* x, long long ldx
     CN_CHECK_LAUNCH();
     return 0;
   });
+}
+
+extern "C" int cn_fp8_quant_static(int dtype, int fmt, const void* x, long long ldx, int P, int C,
+                                   void* y8, long long ldy, const float* state, hipStream_t st) {
+  return with_dtype(dtype, [&](auto tag) {
+    using T = tag_t<decltype(tag)>;
+    if (C % 8 || ldx % 8 || ldy % 8 || !state || !x || !y8 || misaligned(x) || misaligned(y8, 8))
+      return CN_ERR_ALIGN;
+    if (fmt != 0 && fmt != 1) return CN_ERR_UNSUPPORTED;
+    if (C < 8 || ldx < C || ldy < C) return CN_ERR_SHAPE;
+    if (P <= 0) return 0;
+    const int gx = (C / 8 + 63) / 64;
+    int gy = (P + 63) / 64;                      // the grid of cn_fp8_quant_fmt
+    const int maxy = (1024 + gx - 1) / gx;
+    if (gy > maxy) gy = maxy;
+    const dim3 grid(gx, gy);
+    if (fmt == 0)
+      hipLaunchKernelGGL((quant_static_k<T, 0>), grid, dim3(256), 0, st, (const T*)x, ldx, P, C,
+                         (unsigned char*)y8, ldy, state);
+    else
+      hipLaunchKernelGGL((quant_static_k<T, 1>), grid, dim3(256), 0, st, (const T*)x, ldx, P, C,
+                         (unsigned char*)y8, ldy, state);
+    CN_CHECK_LAUNCH();
+    return 0;
+  });
+}
+
+extern "C" int cn_bcast_rows_u8(const void* src, int N, int HW, int C, void* dst, long long ldd,
+                                hipStream_t st) {
+  if (C % 16 || ldd % 16 || !src || !dst || misaligned(src) || misaligned(dst)) return CN_ERR_ALIGN;
+  if (N < 1 || HW < 1 || C < 16 || ldd < C) return CN_ERR_SHAPE;
+  const long long chunks = (long long)N * HW * (C / 16);
+  const long long want = (chunks + 255) / 256;
+  hipLaunchKernelGGL(bcast_rows_u8_k, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(256), 0, st,
+                     (const unsigned char*)src, HW, C / 16, chunks, (unsigned char*)dst, ldd);
+  CN_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int cn_fp8_quant(int dtype, const void* x, long long ldx, int P, int C, void* y8,

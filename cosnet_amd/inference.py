@@ -18,6 +18,10 @@ def multi_reference_x1(model, target, target_depth, searches, search_depths):
     (fp32 NCHW on the GPU) -> mean over the N references of x1, [1,1,H,W] fp32."""
     if model.training:
         raise RuntimeError("multi-reference inference runs in eval mode (test.py:230)")
+    if getattr(model, "fp8_static", None) is not None:
+        # features_nhwc is the per-module path: it would run bf16 convs without saying so
+        raise RuntimeError("multi_reference_x1 does not run static fp8 encoders: use "
+                           "segment_sequence (or set_fp8_static(None))")
     model._set_dtype()
     target, target_depth, searches, search_depths = map(
         model._prep, (target, target_depth, searches, search_depths))
@@ -139,7 +143,8 @@ class FeatureBank:
     def encode(cls, model, rgbs, depths, encode_chunk=8, coatt="bf16"):
         """rgbs [T,3,H,W], depths [T,1,H,W] (fp32 NCHW on the GPU): both encoders over chunks of
         encode_chunk frames, then the two similarity linears (and, coatt = "mxfp8", the MX images),
-        once per frame."""
+        once per frame.  On a model with static fp8 set (model.set_fp8_static) the encoders run
+        fp8_infer.encode_frames_static: e4m3 conv GEMMs on frozen scales; the bank stays bf16."""
         if model.training:
             raise RuntimeError("FeatureBank.encode runs in eval mode (test.py:230)")
         if coatt not in cls.COATT:
@@ -148,14 +153,22 @@ class FeatureBank:
             raise ValueError("coatt='mxfp8' needs the bf16 compute dtype")
         if rgbs.shape[0] != depths.shape[0] or rgbs.shape[0] < 1 or encode_chunk < 1:
             raise ValueError("encode: T >= 1 frames of rgb and depth and encode_chunk >= 1 are expected")
+        static = getattr(model, "fp8_static", None) is not None
+        if static and model.compute_dtype != torch.bfloat16:
+            raise ValueError("static fp8 encoders need the bf16 compute dtype")
         model._set_dtype()
         rgbs, depths = model._prep(rgbs), model._prep(depths)
         t = rgbs.shape[0]
         va = da = None
+        if static:   # e4m3 conv GEMMs on frozen scales (cosnet_amd/fp8_infer.py); the bank stays bf16
+            from .fp8_infer import encode_frames_static
+            feats = lambda enc, x: encode_frames_static(enc, x)
+        else:
+            feats = lambda enc, x: enc.features_nhwc(x)
         for f0 in range(0, t, encode_chunk):
             f1 = min(t, f0 + encode_chunk)
-            v, (_, h, w) = model.encoder.features_nhwc(rgbs[f0:f1])
-            d, dgeo = model.depth_encoder.features_nhwc(depths[f0:f1])
+            v, (_, h, w) = feats(model.encoder, rgbs[f0:f1])
+            d, dgeo = feats(model.depth_encoder, depths[f0:f1])
             if tuple(dgeo[1:]) != (h, w):
                 raise RuntimeError("RGB and depth feature maps differ: %s vs %s" % ((h, w), dgeo[1:]))
             if va is None:

@@ -314,6 +314,23 @@ def fp8_update(states, margin=1.0):
     nv.call("cn_fp8_update", states.data_ptr(), states.numel() // 4, float(margin), nv.stream())
 
 
+def fp8_quant_static(x, state, out=None, fmt=FP8_E4M3):
+    """fp8 bytes of x [P, C] under a frozen state (cn_fp8_quant_static): the state is only read."""
+    p, c = x.shape
+    if out is None:
+        out = torch.empty((p, c), dtype=torch.uint8, device=x.device)
+    nv.call("cn_fp8_quant_static", dtc(x), fmt, x.data_ptr(), ld(x), p, c, out.data_ptr(), ld(out),
+            state.data_ptr(), nv.stream())
+    return out
+
+
+def bcast_rows_u8(src, n, hw, out):
+    """out[(i*hw + p), :] = src[i, :] over bytes (src [n, C] contiguous, out a [n*hw, C] view)."""
+    nv.call("cn_bcast_rows_u8", src.data_ptr(), n, hw, src.shape[1], out.data_ptr(), ld(out),
+            nv.stream())
+    return out
+
+
 def conv_dgrad_fp8(dy8, n, oh, ow, wt8, cin, k, pad, dil, h, w, dy_state, w_state, out=None,
                    accumulate=False):
     """dx (bf16) (+)= conv_dgrad(dy8 e5m2, wt8 e4m3) * s_dy * s_w, stride 1 (fp8 mode)."""
@@ -850,6 +867,25 @@ def bn_apply(x, stats, bn, act=0, prelu=None, res=None, xr=None, rstats=None, rb
             out.data_ptr(), ld(out), nv.ptr(out8), ld(out8) if out8 is not None else 0,
             nv.ptr(qstate), nv.ptr(mask), mask.stride(0) if mask is not None else 0, nv.stream())
     return out
+
+
+def bn_apply_q8(x, stats, bn, qstate, act=0, prelu=None, res=None, xr=None, rstats=None, rbn=None,
+                out=None, out8=None, nseg=1):
+    """bn_apply whose e4m3 image out8 is written under the frozen, read-only qstate
+    (cn_bn_apply_q8: no amax, nothing written to qstate); the bf16 output only into a given
+    `out`.  Returns (out or None, out8)."""
+    p, c = x.shape
+    if out8 is None:
+        out8 = torch.empty((p, c), dtype=torch.uint8, device=x.device)
+    g, b = _affine(bn)
+    rg, rb = _affine(rbn) if rbn is not None else (None, None)
+    nv.call("cn_bn_apply_q8", dtc(x), x.data_ptr(), ld(x), p // nseg, nseg, c, stats[0].data_ptr(),
+            stats[1].data_ptr(), nv.ptr(g), nv.ptr(b), nv.ptr(res), ld(res) if res is not None else 0,
+            nv.ptr(xr), ld(xr) if xr is not None else 0, nv.ptr(rstats[0] if rstats else None),
+            nv.ptr(rstats[1] if rstats else None), nv.ptr(rg), nv.ptr(rb), act, nv.ptr(prelu),
+            nv.ptr(out), ld(out) if out is not None else 0, out8.data_ptr(), ld(out8),
+            qstate.data_ptr(), nv.stream())
+    return out, out8
 
 
 def bn_bwd(x, dy, y, stats, bn, act=0, prelu=None, want_dx=True, dx=None, dres=None, dgamma=None,

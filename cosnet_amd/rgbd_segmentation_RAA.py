@@ -59,6 +59,7 @@ class RGBDSegmentation_RAA(nn.Module):
             raise ValueError("the HIP decoder head is built for num_classes=1 (train.py:379)")
         self.compute_dtype = torch.bfloat16
         self.fp8 = None            # Fp8Context: e4m3 forward conv GEMMs in the encoders (configs[4])
+        self.fp8_static = None     # Fp8Static: frozen-scale e4m3 encoders for inference (set_fp8_static)
         self.pair_encoder = True   # batch frames a and b through each encoder (encoder_fn.py)
         # depth encoder on a second stream (forward()); CN_CONCURRENT_ENCODERS=0 for A/B runs
         self.concurrent_encoders = os.environ.get("CN_CONCURRENT_ENCODERS", "1") != "0"
@@ -148,9 +149,39 @@ class RGBDSegmentation_RAA(nn.Module):
         concurrently with the RGB encoder, and a context's scale update covers all its states."""
         if on and self.compute_dtype != torch.bfloat16:
             raise ValueError("fp8 convs run inside the bf16 path")
+        if on and getattr(self, "fp8_static", None) is not None:
+            raise RuntimeError("set_fp8: static fp8 inference is set (set_fp8_static(None) first)")
         from .fp8 import Fp8Context
         self.fp8 = Fp8Context() if on else None
         self._fp8_depth = Fp8Context() if on else None
+        return self
+
+    def set_fp8_static(self, calibration):
+        """Static-scale fp8 encoders for whole-sequence inference (cosnet_amd/fp8_infer.py): the
+        frozen state tables of an Fp8Calibration are built on the device and every eligible conv
+        weight is quantised now, so nothing is calibrated on first use.  FeatureBank.encode /
+        segment_sequence then run both encoders on e4m3 conv GEMMs whose scales no launch writes.
+        None switches it off; the built state (model.fp8_static) given back switches it on again
+        without rebuilding.  Needs the bf16 compute dtype; exclusive with set_fp8(True)."""
+        if calibration is None:
+            self.fp8_static = None
+            for enc in (self.encoder, self.depth_encoder):
+                enc._cn_fp8_static = None
+            return self
+        if self.compute_dtype != torch.bfloat16:
+            raise ValueError("fp8 convs run inside the bf16 path")
+        if getattr(self, "fp8", None) is not None:
+            raise RuntimeError("set_fp8_static: delayed-scaling fp8 is set (set_fp8(False) first)")
+        from .fp8_infer import Fp8Static
+        if isinstance(calibration, Fp8Static):   # a state this model built before: switched back on
+            st = calibration
+            if st.model() is not self:
+                raise ValueError("set_fp8_static: the static fp8 state was built for another model")
+        else:
+            st = Fp8Static(self, calibration)
+        self.fp8_static = st
+        self.encoder._cn_fp8_static = st.encoders["encoder"]
+        self.depth_encoder._cn_fp8_static = st.encoders["depth_encoder"]
         return self
 
     def _set_dtype(self):
@@ -170,6 +201,11 @@ class RGBDSegmentation_RAA(nn.Module):
         return s
 
     def forward(self, rgbs_a, rgbs_b, depths_a, depths_b, stages=None):
+        if getattr(self, "fp8_static", None) is not None:
+            # the pair forward would run bf16 convs (and, in train mode, has a backward)
+            raise RuntimeError("static fp8 is an inference path of the feature bank "
+                               "(inference.segment_sequence); set_fp8_static(None) to train or "
+                               "to run the pair forward")
         self._set_dtype()
         rgbs_a, rgbs_b, depths_a, depths_b = map(self._prep, (rgbs_a, rgbs_b, depths_a, depths_b))
         input_size = tuple(rgbs_a.shape[2:])
@@ -257,7 +293,9 @@ class RGBDSegmentation_RAA(nn.Module):
         MX-fp8 images of its bf16 features) runs the fp8 co-attention of both modalities in one
         launch (ops.coatt_f8_idx); gate, reduce conv, BN and classifier are unchanged.  Eval mode
         under no_grad; the model's own fp8 mode (set_fp8: fp8 encoder convs with delayed scaling,
-        whose features depend on the order of calls) stays refused."""
+        whose features depend on the order of calls) stays refused.  Static fp8 (set_fp8_static:
+        frozen scales, so a frame's features depend on the frame alone) is accepted: its bank is
+        four bf16 tensors like any other."""
         if self.training or torch.is_grad_enabled():
             raise RuntimeError("head_a_indexed is an inference path: eval mode under torch.no_grad()")
         if getattr(self, "fp8", None) is not None:

@@ -117,6 +117,11 @@ int cn_fp8_quant_multi(const void* recs, int n, hipStream_t stream);
 /* scale = amax * margin / fmt max (state[3], default 448) for each of nstates consecutive
  * states; amax reset */
 int cn_fp8_update(float* states, int nstates, float margin, hipStream_t stream);
+/* Static scaling (inference): y8 = fp8(clamp(x * state[1])) with the rounding and saturation of
+ * mode 0, the state READ-ONLY: no amax, no atomic, no reduction, so the bytes depend on x and the
+ * frozen scale alone.  x / y8 as cn_fp8_quant_fmt (x 16-byte, y8 8-byte aligned). */
+int cn_fp8_quant_static(int dtype, int fmt, const void* x, long long ldx, int P, int C, void* y8,
+                        long long ldy, const float* state, hipStream_t stream);
 /* dx (bf16) (+)= conv_dgrad(dy8, wt8) * dy_state[0] * w_state[0], stride 1 (replaces the
  * backward of nn.Conv2d w.r.t. its input, deeplab/residual_net.py:59-67 autograd, in fp8 mode):
  * dy8 e5m2 [N*OH*OW][Cout] (cn_fp8_quant_fmt fmt 1), wt8 e4m3 [Cin][KH][KW][Cout]; block-scaled
@@ -239,6 +244,18 @@ int cn_bn_apply_ex(int dtype, const void* x, long long ldx, int P, int nseg, int
                    const float* rbeta, int act, const float* prelu, void* y, long long ldy,
                    void* y8, long long ldy8, float* qstate, unsigned char* mask, long long ldm,
                    hipStream_t stream);
+/* Inference with frozen fp8 scales (cosnet_amd/fp8_infer.py): the apply of cn_bn_apply_fp8 with
+ * qstate READ-ONLY -- y8 = e4m3(clamp(t * qstate[1])) of the fp32 activation t, the bytes
+ * cn_bn_apply_fp8 writes for the same state, but no amax is collected and nothing is written to
+ * qstate.  y (bf16) is written only when non-null: an activation that only fp8 convs read exists
+ * as bytes alone.  bf16 only; CN_ERR_ALIGN for fp32 input, a null y8 / qstate, ldy8 % 16, a
+ * misaligned pointer or leading dimension; CN_ERR_SHAPE for P < 1, nseg < 1, ldy8 < C. */
+int cn_bn_apply_q8(int dtype, const void* x, long long ldx, int P, int nseg, int C,
+                   const float* mean, const float* invstd, const float* gamma, const float* beta,
+                   const void* res, long long ldr, const void* xr, long long ldxr,
+                   const float* rmean, const float* rinvstd, const float* rgamma,
+                   const float* rbeta, int act, const float* prelu, void* y, long long ldy,
+                   void* y8, long long ldy8, const float* qstate, hipStream_t stream);
 /* launch-shape knobs (blocks / rows per thread of each BN pass), for tuning only */
 int cn_bn_set_tuning(int key, int value);
 /* backward of cn_bn_apply w.r.t. x (train mode), masks fused; dres <- dz for the residual.
@@ -413,6 +430,10 @@ int cn_avgpool(int dtype, const void* x, long long ld, int N, int HW, int C, flo
 size_t cn_avgpool_workspace_floats(int dtype, int N, int HW, int C);
 int cn_bcast_rows(int dtype, const void* src, int N, int HW, int C, float scale, void* dst,
                   long long ld, int accumulate, hipStream_t stream);
+/* the byte form: dst[(n*HW + p)*ld + c] = src[n*C + c] (fp8 images; C % 16 == 0, ld % 16 == 0,
+ * 16-byte aligned pointers) */
+int cn_bcast_rows_u8(const void* src, int N, int HW, int C, void* dst, long long ld,
+                     hipStream_t stream);
 /* gate: rgbd_segmentation_RAA.py:177-184 (RGB, no bias), :228-235 (depth, bias) */
 int cn_gate_fwd(int dtype, const void* z, long long ldz, int P, int C, const float* g,
                 const float* gb, void* out, long long ldo, float* mask, hipStream_t stream);

@@ -17,7 +17,9 @@ load with torch.load(weights_only=True); "module." prefixes are stripped (test.p
 `--feature-bank` (sbmrgbd): the references of a target are frames of its own sequence, so each
 sequence's frames are loaded and encoded ONCE and the pairs are formed by index
 (cosnet_amd.inference.segment_sequence); same log lines, order and PNGs.  With it,
-`--coatt mxfp8` (bf16 only) runs the bank's co-attention on MX-fp8 images of the features.
+`--coatt mxfp8` (bf16 only) runs the bank's co-attention on MX-fp8 images of the features, and
+`--dtype fp8 [--fp8-calibration FILE]` runs the encoders' conv GEMMs on e4m3 operands under
+calibrated, frozen scales (cosnet_amd/fp8_infer.py); the two compose.
 """
 import argparse
 import datetime
@@ -46,8 +48,10 @@ def get_arguments(argv=None):
     # this build
     p.add_argument("--config", default=os.path.join(REPO, "config.yaml"))
     p.add_argument("--checkpoint", default=None, help="overrides test.model.<name>.pretrained_params")
-    p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"],
-                   help="bf16 (default): the MI355X throughput path, fused co-attention; fp32: the reference arithmetic")
+    p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"],
+                   help="bf16 (default): the MI355X throughput path, fused co-attention; fp32: the reference "
+                        "arithmetic; fp8 (--feature-bank): the bf16 path with the encoders' conv GEMMs on e4m3 "
+                        "operands under calibrated, frozen scales (cosnet_amd/fp8_infer.py)")
     p.add_argument("--result-root", default=".")
     p.add_argument("--frames", type=int, default=None, help="synthetic: number of target frames")
     p.add_argument("--feature-bank", action="store_true",
@@ -56,11 +60,21 @@ def get_arguments(argv=None):
     p.add_argument("--coatt", default="bf16", choices=["bf16", "mxfp8"],
                    help="--feature-bank: the bank's co-attention.  bf16 (default): the bf16 indexed kernel; "
                         "mxfp8: MX-fp8 images of the bf16 features, each frame quantised once per sequence")
+    p.add_argument("--fp8-calibration", default=None, metavar="FILE",
+                   help="--dtype fp8: the calibration (JSON).  Loaded if the file exists; otherwise made "
+                        "before evaluation from the first --fp8-calibration-frames test frames and written there")
+    p.add_argument("--fp8-calibration-frames", type=int, default=16)
     args = p.parse_args(argv)
     if args.coatt == "mxfp8" and not args.feature_bank:
         p.error("--coatt mxfp8 needs --feature-bank")
-    if args.coatt == "mxfp8" and args.dtype != "bf16":
-        p.error("--coatt mxfp8 needs --dtype bf16")
+    if args.coatt == "mxfp8" and args.dtype not in ("bf16", "fp8"):
+        p.error("--coatt mxfp8 needs --dtype bf16 (or fp8, whose features are bf16)")
+    if args.dtype == "fp8" and not args.feature_bank:
+        p.error("--dtype fp8 needs --feature-bank")
+    if args.dtype == "fp8" and args.fp8_calibration_frames < 1:
+        p.error("--fp8-calibration-frames must be at least 1")
+    if args.dtype != "fp8" and args.fp8_calibration:
+        p.error("--fp8-calibration needs --dtype fp8")
     return args
 
 
@@ -115,7 +129,7 @@ def main(argv=None):
     logger.write(LOG_START + str(args) + LOG_END + "\n")
     logger.flush()
 
-    model = C.build_model(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
+    model = C.build_model(torch.float32 if args.dtype == "fp32" else torch.bfloat16)
     if ckpt:
         model.load_state_dict(convert_state_dict(load_checkpoint(ckpt)["model"]))
     else:
@@ -148,6 +162,19 @@ def main(argv=None):
             os.makedirs(d, exist_ok=True)
             Image.fromarray(mask).save(os.path.join(d, "%s.png" % frame))
 
+    def static_fp8(load_frames):
+        """--dtype fp8: the calibration file if it exists, else one made from load_frames(k) =
+        (rgbs, depths) of the first k test frames (and written to the file, if one is named)."""
+        from cosnet_amd.fp8_infer import Fp8Calibration, calibrate
+        path = args.fp8_calibration
+        if path and os.path.exists(path):
+            calib = Fp8Calibration.load(path)
+        else:
+            calib = calibrate(model, *load_frames(args.fp8_calibration_frames))
+            if path:
+                calib.save(path)
+        model.set_fp8_static(calib)
+
     db = None
     if args.dataset == "sbmrgbd":
         from cosnet_amd.sbm_rgbd import SBMRGBD
@@ -162,6 +189,11 @@ def main(argv=None):
             # and encoded once, targets scored and logged in index order
             frames = sbm.sets[sbm.stage]["names_of_frames"]
             n = len(sbm)
+            if args.dtype == "fp8":   # test-stage frames in list order; loading draws nothing from the RNG
+                def first_frames(k):
+                    fr = [sbm.load_frame(frames[i]) for i in range(min(k, n))]
+                    return torch.stack([f[0] for f in fr]), torch.stack([f[1] for f in fr])
+                static_fp8(first_frames)
             plans = [sbm.reference_plan(i) for i in range(n)]
             k = 0
             while k < n:
@@ -186,6 +218,12 @@ def main(argv=None):
     elif args.dataset == "synthetic":
         db = SyntheticRGBDPairs(args.frames // args.batch_size, args.image_HW_4_model, args.batch_size,
                                 sample_range=args.sample_range, seed=4321)
+        if args.dtype == "fp8":
+            def first_targets(k):
+                bs = [db[i] for i in range(min(len(db), -(-k // args.batch_size)))]
+                return (torch.cat([b["target"] for b in bs])[:k].to(dev),
+                        torch.cat([b["target_depth"] for b in bs])[:k].to(dev))
+            static_fp8(first_targets)
     else:
         raise SystemExit("dataset %r: only sbmrgbd and synthetic are provided by this build" % args.dataset)
     for index, batch in enumerate(db or ()):

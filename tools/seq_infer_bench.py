@@ -18,6 +18,11 @@ bf16, the indexed bf16 kernel).  The result then also holds the one-off image bu
 (both modalities, timed on its own over the rounds; it is part of the bank's encoder stage) and
 the outputs against the bf16 bank's on the same sequence.  To compare the two settings, alternate
 runs of this tool with --coatt bf16 and --coatt mxfp8 on one device.
+
+--dtype fp8 times the bank path with static-scale fp8 encoders (cosnet_amd/fp8_infer.py),
+calibrated on the tool's own sequence before timing; the per-target path stays bf16 and the result
+also holds the fp8 bank's outputs against the bf16 bank's.  Alternate runs with --dtype bf16 and
+--dtype fp8 to compare.
 """
 import argparse
 import json
@@ -43,7 +48,9 @@ def parse():
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--nref", type=int, default=5)
     ap.add_argument("--size", type=int, default=473)
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "fp8"],
+                    help="fp8: the bank path's encoders on static-scale e4m3 conv GEMMs, calibrated on "
+                         "this sequence before timing (the per-target path stays bf16)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -52,8 +59,8 @@ def parse():
     ap.add_argument("--coatt", default="bf16", choices=["bf16", "mxfp8"],
                     help="the bank path's co-attention (mxfp8: MX-fp8 images, --dtype bf16 only)")
     a = ap.parse_args()
-    if a.coatt == "mxfp8" and a.dtype != "bf16":
-        ap.error("--coatt mxfp8 needs --dtype bf16")
+    if a.coatt == "mxfp8" and a.dtype == "fp32":
+        ap.error("--coatt mxfp8 needs --dtype bf16 or fp8")
     return a
 
 
@@ -96,7 +103,7 @@ def main():
         raise SystemExit("seq_infer_bench: needs the GPU (no timing without one)")
     dev = torch.device("cuda:0")
     T, N, H = a.frames, a.nref, a.size
-    dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
+    dt = torch.float32 if a.dtype == "fp32" else torch.bfloat16
     m = C.build_model(dt)
     sd = recipe_state_dict(m.state_dict())
     calib = os.path.join(REPO, "tests", "golden", "bn_calibration_473.npz")
@@ -119,9 +126,27 @@ def main():
         return torch.cat([multi_reference_x1(m, rgbs[t:t + 1], deps[t:t + 1], rgbs[ridx[t]], deps[ridx[t]])
                           for t in range(T)])
 
+    # --dtype fp8: calibrated on this sequence, tables and e4m3 weights built once; the bank path
+    # switches the built state on around its calls (two attribute writes), the per-target path and
+    # the bf16 reference bank run with it off
+    static = None
+    if a.dtype == "fp8":
+        from cosnet_amd.fp8_infer import calibrate
+        static = m.set_fp8_static(calibrate(m, rgbs, deps, a.encode_chunk)).fp8_static
+        m.set_fp8_static(None)
+
+    def with_static(fn):
+        if static is None:
+            return fn()
+        m.set_fp8_static(static)
+        try:
+            return fn()
+        finally:
+            m.set_fp8_static(None)
+
     def bank():
-        return segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk, pair_chunk=a.pair_chunk,
-                                coatt=a.coatt)
+        return with_static(lambda: segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk,
+                                                    pair_chunk=a.pair_chunk, coatt=a.coatt))
 
     # ---- stage split: the same calls with events between the stages -------------------------------
     @torch.no_grad()
@@ -153,7 +178,8 @@ def main():
     @torch.no_grad()
     def bank_stages(st):
         ia, ib = plan_pairs(T, list(range(T)), refs)
-        b = st.run("encoder", lambda: FeatureBank.encode(m, rgbs, deps, a.encode_chunk, a.coatt))
+        b = st.run("encoder", lambda: with_static(
+            lambda: FeatureBank.encode(m, rgbs, deps, a.encode_chunk, a.coatt)))
         step = max(1, a.pair_chunk // N)
 
         def head():
@@ -197,6 +223,13 @@ def main():
                  "vs_bf16_bank": {"mask_agreement": float(((fm > 0.5) == (ref > 0.5)).double().mean()),
                                   "mean_abs_diff": float((fm - ref).abs().mean()),
                                   "max_abs_diff": float((fm - ref).abs().max())}}
+    if static is not None:   # the static-fp8 bank against the bf16 bank (same co-attention setting)
+        ref = segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk, pair_chunk=a.pair_chunk,
+                               coatt=a.coatt).double().cpu()
+        fm = out_b.double().cpu()
+        extra["fp8_vs_bf16_bank"] = {"mask_agreement": float(((fm > 0.5) == (ref > 0.5)).double().mean()),
+                                     "mean_abs_diff": float((fm - ref).abs().mean()),
+                                     "max_abs_diff": float((fm - ref).abs().max())}
     fa, fb = out_a.double().cpu(), out_b.double().cpu()
     stat = lambda v: {"mean": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v)),
                       "spread": float((np.max(v) - np.min(v)) / np.mean(v))}
