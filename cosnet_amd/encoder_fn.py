@@ -11,14 +11,27 @@ reference differentiates.
 
 Reference blocks: stem deeplab/residual_net.py:157-160, Bottleneck :74-96, ASPP
 deeplab/deeplabv3_encoder.py:50-86.
+
+The forward saves one named record per module (StemRec, BlockRec, AsppRec), read by field name by
+the backwards, fp8_infer.py's calibration walk and the tests.  The walks over an encoder here, in
+fp8_infer.py and in tools/ take its structure from layers / blocks / layer_of / aspp_branches.
+
+Two forward variants were measured and not adopted (profiles/r06_aspp_grouped_fp8_stats_ab.txt);
+their switches were removed afterwards, source at commit c31c537, the kernels and their ops
+wrappers stay: the ASPP's three atrous convs as one grouped launch (cn_conv_fwd_bn_grouped,
+CN_ASPP_GROUPED: level with the three launches in the two-stream step, where the depth stream
+already fills the CUs a one-round launch leaves idle), and the BN statistics of the long-K narrow
+fp8 convs from the fp8 GEMM's epilogue (cn_conv_fwd_fp8_bn, CN_FP8_FUSE_STATS: 0.8 % slower on
+the configs[4] step, the fp8 tiles' epilogue being long next to their K loop).
 """
+import collections
 import os
 
 import torch
 
 from . import _native as nv
 from . import ops
-from .fp8 import fp8_ok
+from .fp8 import fp8_conv_ok
 from .ops import WCACHE, as_param_grad, bn_apply, bn_bwd, bn_stats, conv_dgrad, conv_fwd, conv_wgrad
 
 from .functions import F, _GRAD
@@ -60,16 +73,6 @@ WGRAD_GSPLIT = int(os.environ.get("CN_WGRAD_GSPLIT", "512"))
 # fp8 mode (configs[4]): the 3x3 bottleneck and ASPP weight gradients on fp8 operands
 # (cn_conv_wgrad_fp8); CN_WGRAD_FP8=0 keeps them bf16 (A/B runs).
 WGRAD_FP8 = os.environ.get("CN_WGRAD_FP8", "1") != "0"
-# The ASPP's three atrous convs in one grouped launch (cn_conv_fwd_bn_grouped, train mode, bf16 /
-# fp32): measured level with the three launches in the two-stream step (the depth stream already
-# fills the CUs a one-round launch leaves idle; profiles/r06_aspp_grouped_fp8_stats_ab.txt), so
-# off by default; CN_ASPP_GROUPED=1 selects it.
-ASPP_GROUPED = os.environ.get("CN_ASPP_GROUPED", "0") == "1"
-# fp8 mode: the BN statistics of the long-K narrow fp8 convs (fuse_stats) from the fp8 GEMM's
-# epilogue (cn_conv_fwd_fp8_bn) instead of their own pass: measured 0.8 % SLOWER on the configs[4]
-# step (the fp8 tiles' epilogue is long next to their K loop), so off by default;
-# CN_FP8_FUSE_STATS=1 selects it.
-FP8_FUSE_STATS = os.environ.get("CN_FP8_FUSE_STATS", "0") == "1"
 
 
 # The per-module path (functions.StemFn / BottleneckFn / ASPPFn: frames of different sizes, e.g.
@@ -93,11 +96,40 @@ class no_fp8:
         return False
 
 
-def _layer_index(enc):
-    """id(block) -> index of its ResNet layer."""
+# ---- the encoder's structure: stem, four layers of bottlenecks, ASPP -----------------------------
+def layers(enc):
     bb = enc.backbone
-    return {id(blk): i for i, layer in enumerate((bb.layer1, bb.layer2, bb.layer3, bb.layer4))
-            for blk in layer}
+    return (bb.layer1, bb.layer2, bb.layer3, bb.layer4)
+
+
+def blocks(enc):
+    return [blk for layer in layers(enc) for blk in layer]
+
+
+def layer_of(enc):
+    """block -> index of its ResNet layer."""
+    return {blk: i for i, layer in enumerate(layers(enc)) for blk in layer}
+
+
+def aspp_branches(mod):
+    """(conv, bn, k, dilation) of the ASPP's conv branches in concat order (after the pooled
+    branch's 512 columns): the 1x1, then one 3x3 per entry of mod.cn_dilations."""
+    return [(mod.conv2d_0, mod.bn_0, 1, 0)] + [
+        (getattr(mod, "conv2d_%d" % (i + 1)), getattr(mod, "bn_%d" % (i + 1)), 3, dd)
+        for i, dd in enumerate(mod.cn_dilations)]
+
+
+# ---- what the forward saves ---------------------------------------------------------------------
+# One record per module: the module, the tensors its backward reads (c*: raw conv outputs, y*:
+# activations, st*: SegStats, w*t: transposed weights for the dgrads, q*: Saved8 e4m3 inputs for
+# the fp8 weight gradients or None; the ASPP's cs / sts / wts / q8s: one entry per
+# aspp_branches(mod)), then the geometry (n: images per frame segment).
+StemRec = collections.namedtuple("StemRec", "mod x c y am st n cimg h w oh ow ph pw")
+BlockRec = collections.namedtuple(
+    "BlockRec", "mod x c1 y1 c2 y2 c3 cd mk st1 st2 st3 std w1t w2t w3t wdt q2 "
+                "n h w oh ow s d planes cin")
+AsppRec = collections.namedtuple(
+    "AsppRec", "mod x pool cp yp stp wct cs sts wts cat cb stb wbt out q8s qb n h w")
 
 
 class WgradQueue:
@@ -189,32 +221,26 @@ def fuse_bwd(cin, kdim):
 
 
 def conv_bn(x, n, h, w, wf, cout, k, stride, pad, dil, bn, training, nseg, bias=None, weight=None,
-            q8=None):
-    """conv -> raw output c and the BN statistics of c per segment.  Train mode: the statistics
-    come out of the conv's GEMM epilogue where that is cheaper (ops.conv_fwd_bn, no pass over c),
-    else a separate statistics pass; eval: running statistics.  fp8 mode (configs[4]): the
-    conv GEMM takes e4m3 operands (cosnet_amd/fp8.py), statistics from its epilogue by the same
-    rule (ops.conv_fwd_fp8_bn) or the separate pass; with a list q8 the e4m3 input copy is
-    appended to it as Fp8Acts.saved() (for the fp8 weight gradient)."""
+            keep8=False):
+    """conv -> (c, oh, ow, st, q8): raw output c, the BN statistics of c per segment and the
+    saved e4m3 input or None.  Train mode: the statistics come out of the conv's GEMM epilogue
+    where that is cheaper (ops.conv_fwd_bn, no pass over c), else a separate statistics pass;
+    eval: running statistics.  fp8 mode (configs[4]): the conv GEMM takes e4m3 operands
+    (cosnet_amd/fp8.py, fp8_conv_ok), statistics by the separate pass; with keep8 q8 is the e4m3
+    input copy as Fp8Acts.saved() (for the fp8 weight gradient)."""
     cin = wf.shape[1] // (k * k)
     ctx = fp8_of(bn)
-    if weight is not None and ctx is not None and fp8_ok(x, cin) and x.shape[0] > 64:
+    if weight is not None and ctx is not None and fp8_conv_ok(x, cin):
         x8, xs = ctx.acts.quant(x, id(weight))
-        if q8 is not None:
-            q8.append(ctx.acts.saved(x8, xs))
+        q8 = ctx.acts.saved(x8, xs) if keep8 else None
         wf8, ws = ctx.weights.get(weight)
-        if training and FP8_FUSE_STATS and fuse_stats(cout, wf.shape[1]):
-            # the statistics from the fp8 GEMM's epilogue, as the bf16 path takes them (round 6)
-            c, oh, ow, st = ops.conv_fwd_fp8_bn(x8, n, h, w, wf8, cout, k, stride, pad, dil, xs, ws,
-                                                bn, nseg, bias=bias)
-            return c, oh, ow, SegStats(st, nseg, cout)
         c, oh, ow = ops.conv_fwd_fp8(x8, n, h, w, wf8, cout, k, stride, pad, dil, xs, ws, bias=bias)
-        return c, oh, ow, seg_stats(c, bn, training, nseg)
+        return c, oh, ow, seg_stats(c, bn, training, nseg), q8
     if training and fuse_stats(cout, wf.shape[1]):
         c, oh, ow, st = ops.conv_fwd_bn(x, n, h, w, wf, cout, k, stride, pad, dil, bn, nseg, bias=bias)
-        return c, oh, ow, SegStats(st, nseg, cout)
+        return c, oh, ow, SegStats(st, nseg, cout), None
     c, oh, ow = conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=bias)
-    return c, oh, ow, seg_stats(c, bn, training, nseg)
+    return c, oh, ow, seg_stats(c, bn, training, nseg), None
 
 
 def seg_apply(x, stats, bn, act=0, prelu=None, res=None, xr=None, rstats=None, rbn=None, out=None,
@@ -249,7 +275,7 @@ def stem_fwd(res, imgs, nseg, dt, rec):
         nv.call("cn_nchw_to_nhwc", nv.dtype_code(dt), img.data_ptr(), n1, cimg, h, w, 8,
                 x[i * n1 * h * w:].data_ptr(), nv.stream())
     wf, _ = WCACHE.get(res.conv1.weight, dt, cin_pad=8, need_t=False)
-    c, oh, ow, st = conv_bn(x, n, h, w, wf, 64, 7, 2, 3, 1, res.bn1, res.training, nseg)
+    c, oh, ow, st, _ = conv_bn(x, n, h, w, wf, 64, 7, 2, 3, 1, res.bn1, res.training, nseg)
     y = seg_apply(c, st, res.bn1, act=1)
     ph, pw = ops.pool_out(oh), ops.pool_out(ow)
     out = torch.empty((n * ph * pw, 64), dtype=dt, device=x.device)
@@ -257,20 +283,20 @@ def stem_fwd(res, imgs, nseg, dt, rec):
     nv.call("cn_maxpool_fwd", nv.dtype_code(dt), y.data_ptr(), n, oh, ow, 64, ph, pw, 3, 2, 1,
             out.data_ptr(), am.data_ptr(), nv.stream())
     if rec is not None:
-        rec.append(("stem", res, (x, c, y, am, st), (n1, cimg, h, w, oh, ow, ph, pw)))
+        rec.append(StemRec(res, x, c, y, am, st, n1, cimg, h, w, oh, ow, ph, pw))
     return out, (n, ph, pw)
 
 
-def stem_bwd(item, dout, grads):
-    _, res, (x, c, y, am, st), (n1, cimg, h, w, oh, ow, ph, pw) = item
+def stem_bwd(r, dout, grads):
+    res, n1, h, w, oh, ow = r.mod, r.n, r.h, r.w, r.oh, r.ow
     pa = n1 * oh * ow
     dy = torch.empty((pa, 64), dtype=dout.dtype, device=dout.device)
-    nv.call("cn_maxpool_bwd", ops.dtc(dout), dout.data_ptr(), am.data_ptr(), n1, oh, ow, 64, ph,
-            pw, 3, 2, 1, dy.data_ptr(), nv.stream())
-    dc, dg, db, _ = bn_bwd(c[:pa], dy, None, st[0], res.bn1, act=1,
+    nv.call("cn_maxpool_bwd", ops.dtc(dout), dout.data_ptr(), r.am.data_ptr(), n1, oh, ow, 64, r.ph,
+            r.pw, 3, 2, 1, dy.data_ptr(), nv.stream())
+    dc, dg, db, _ = bn_bwd(r.c[:pa], dy, None, r.st[0], res.bn1, act=1,
                            dgamma=grads.buf(res.bn1.weight, 64), dbeta=grads.buf(res.bn1.bias, 64))
-    dw = conv_wgrad(x[:n1 * h * w], n1, h, w, 8, dc, oh, ow, 64, 7, 2, 3, 1)
-    grads[res.conv1.weight] = dw.view(64, 7, 7, 8)[..., :cimg].permute(0, 3, 1, 2)
+    dw = conv_wgrad(r.x[:n1 * h * w], n1, h, w, 8, dc, oh, ow, 64, 7, 2, 3, 1)
+    grads[res.conv1.weight] = dw.view(64, 7, 7, 8)[..., :r.cimg].permute(0, 3, 1, 2)
     grads[res.bn1.weight] = dg
     grads[res.bn1.bias] = db
 
@@ -279,19 +305,18 @@ def fp8_dgrad_ok(dy, k):
     """fp8 dgrad (e5m2 dY x e4m3 W^T) for the compute-heavy stride-1 convs: K = k*k*Cout >= 2304
     (the layer-3/4 3x3 convs, the ASPP convs); the short-K 1x1 dgrads are HBM-bound and gain
     nothing from a 2x MFMA rate."""
-    return (dy.dtype == torch.bfloat16 and k * k * dy.shape[1] >= 2304 and dy.shape[1] % 16 == 0
-            and ops.ld(dy) % 16 == 0 and dy.shape[0] > 64)
+    return k * k * dy.shape[1] >= 2304 and fp8_conv_ok(dy, dy.shape[1])
 
 
 def wgrad_f8(ctx, q8, dy, rows, k, weight, cin):
     """fp8 operands for a weight gradient (configs[4]) when both exist: the forward's e4m3 input
-    copy (q8 = Fp8Acts.saved(), frame-a `rows`) and an e5m2 output gradient the fp8 dgrad quantises
-    (fp8_dgrad_ok; the same pass-cached copy serves both).  (x8, x_state, dy8, dy_state) or None."""
-    if ctx is None or not q8 or not fp8_dgrad_ok(dy, k) or cin % 16:
+    copy (q8 = Fp8Acts.saved() or None, frame-a `rows`) and an e5m2 output gradient the fp8 dgrad
+    quantises (fp8_dgrad_ok; the same pass-cached copy serves both).  (x8, x_state, dy8, dy_state)
+    or None."""
+    if ctx is None or q8 is None or not fp8_dgrad_ok(dy, k) or cin % 16:
         return None
-    x8, handle, slot = q8[0]
     dy8, ds = ctx.grads.quant(dy, ("dgrad", id(weight)))
-    return x8[:rows], handle.state(slot), dy8, ds
+    return q8.x8[:rows], q8.handle.state(q8.slot), dy8, ds
 
 
 def wgrad_now(x, n, h, w, cin, dy, oh, ow, cout, k, stride, pad, dil, dw=None, f8=None):
@@ -343,16 +368,15 @@ def bottleneck_fwd(blk, x, geo, nseg, rec):
     w1f, w1t = WCACHE.get(blk.conv1.weight, dt)
     w2f, w2t = WCACHE.get(blk.conv2.weight, dt)
     w3f, w3t = WCACHE.get(blk.conv3.weight, dt)
-    c1, oh, ow, st1 = conv_bn(x, n, h, w, w1f, planes, 1, s, 0, 1, blk.bn1, tr, nseg,
-                              weight=blk.conv1.weight)
+    c1, oh, ow, st1, _ = conv_bn(x, n, h, w, w1f, planes, 1, s, 0, 1, blk.bn1, tr, nseg,
+                                 weight=blk.conv1.weight)
     y1 = seg_apply(c1, st1, blk.bn1, act=1, fp8_key=id(blk.conv2.weight))
     # the e4m3 input copy is kept for the backward only when the fp8 weight gradient reads it
-    q2 = [] if rec is not None and WGRAD_FP8 else None
-    c2, _, _, st2 = conv_bn(y1, n, oh, ow, w2f, planes, 3, 1, d, d, blk.bn2, tr, nseg,
-                            weight=blk.conv2.weight, q8=q2)
+    c2, _, _, st2, q2 = conv_bn(y1, n, oh, ow, w2f, planes, 3, 1, d, d, blk.bn2, tr, nseg,
+                                weight=blk.conv2.weight, keep8=rec is not None and WGRAD_FP8)
     y2 = seg_apply(c2, st2, blk.bn2, act=1, fp8_key=id(blk.conv3.weight))
-    c3, _, _, st3 = conv_bn(y2, n, oh, ow, w3f, 4 * planes, 1, 1, 0, 1, blk.bn3, tr, nseg,
-                            weight=blk.conv3.weight)
+    c3, _, _, st3, _ = conv_bn(y2, n, oh, ow, w3f, 4 * planes, 1, 1, 0, 1, blk.bn3, tr, nseg,
+                               weight=blk.conv3.weight)
     cd = std = wdt = None
     # the backward of the residual BN + ReLU needs only y > 0: kept as bits (1/16 of y's bytes),
     # read by bn_bwd(act=4) instead of y (deeplab/residual_net.py:107-109)
@@ -360,60 +384,59 @@ def bottleneck_fwd(blk, x, geo, nseg, rec):
     if blk.downsample is not None:
         wdf, wdt = WCACHE.get(blk.downsample[0].weight, dt)
         bnd = blk.downsample[1]
-        cd, _, _, std = conv_bn(x, n, h, w, wdf, 4 * planes, 1, s, 0, 1, bnd, tr, nseg,
-                                weight=blk.downsample[0].weight)
+        cd, _, _, std, _ = conv_bn(x, n, h, w, wdf, 4 * planes, 1, s, 0, 1, bnd, tr, nseg,
+                                   weight=blk.downsample[0].weight)
         y = seg_apply(c3, st3, blk.bn3, act=1, xr=cd, rstats=std, rbn=bnd, fp8_key=("out", id(blk)),
                       mask=mk)
     else:
         y = seg_apply(c3, st3, blk.bn3, act=1, res=x, fp8_key=("out", id(blk)), mask=mk)
     if rec is not None:
-        rec.append(("block", blk, (x, c1, y1, c2, y2, c3, cd, mk, st1, st2, st3, std, w1t, w2t, w3t, wdt, q2),
-                    (n // nseg, h, w, oh, ow, s, d, planes, x.shape[1])))
+        rec.append(BlockRec(blk, x, c1, y1, c2, y2, c3, cd, mk, st1, st2, st3, std, w1t, w2t, w3t, wdt,
+                            q2, n // nseg, h, w, oh, ow, s, d, planes, x.shape[1]))
     return y, (n, oh, ow)
 
 
-def bottleneck_bwd(item, dy, grads, need_dx=True, wq=None):
+def bottleneck_bwd(r, dy, grads, need_dx=True, wq=None):
     """Backward of one bottleneck; with a WgradQueue the four weight gradients are queued (their
     dW buffers are registered in `grads` now and filled by wq.flush())."""
-    _, blk, sv, (n, h, w, oh, ow, s, d, planes, cin) = item
+    blk, s, d, planes, cin = r.mod, r.s, r.d, r.planes, r.cin
+    n, h, w, oh, ow = r.n, r.h, r.w, r.oh, r.ow
     wgrad = conv_wgrad if wq is None else wq.add
-    x, c1, y1, c2, y2, c3, cd, mk, st1, st2, st3, std, w1t, w2t, w3t, wdt, q2 = sv
     pi, po = n * h * w, n * oh * ow                     # frame-a rows in / out
-    x, c1, y1, c2, y2, c3, mk = x[:pi], c1[:po], y1[:po], c2[:po], y2[:po], c3[:po], mk[:po]
-    has_down = cd is not None
+    x, c1, y1, c2, y2, c3, mk = r.x[:pi], r.c1[:po], r.y1[:po], r.c2[:po], r.y2[:po], r.c3[:po], r.mk[:po]
+    has_down = r.cd is not None
     dx = None
     g3o, b3o = grads.buf(blk.bn3.weight, 4 * planes), grads.buf(blk.bn3.bias, 4 * planes)
     if has_down:
-        cd = cd[:po]
-        dc3, dg3, db3, _ = bn_bwd(c3, dy, mk, st3[0], blk.bn3, act=4, dgamma=g3o, dbeta=b3o)
-        dcd, _, _, _ = bn_bwd(cd, dy, mk, std[0], blk.downsample[1], act=4)
+        dc3, dg3, db3, _ = bn_bwd(c3, dy, mk, r.st3[0], blk.bn3, act=4, dgamma=g3o, dbeta=b3o)
+        dcd, _, _, _ = bn_bwd(r.cd[:po], dy, mk, r.std[0], blk.downsample[1], act=4)
     else:
         dx = torch.empty_like(x)
-        dc3, dg3, db3, _ = bn_bwd(c3, dy, mk, st3[0], blk.bn3, act=4, dres=dx, dgamma=g3o, dbeta=b3o)
+        dc3, dg3, db3, _ = bn_bwd(c3, dy, mk, r.st3[0], blk.bn3, act=4, dres=dx, dgamma=g3o, dbeta=b3o)
     dw3 = wgrad(y2, n, oh, ow, planes, dc3, oh, ow, 4 * planes, 1, 1, 0, 1,
                 dw=grads.buf(blk.conv3.weight, 4 * planes, planes))
     # dgrads, fused with the reduction of the backward of the BN + ReLU that fed the conv where
     # that is cheaper (fuse_bwd)
     f8 = fp8_of(blk.bn2)
-    dc2, dg2, db2 = dgrad_bn_bwd(dc3, n, oh, ow, w3t, planes, 1, 0, 1, c2, st2[0], blk.bn2, grads,
+    dc2, dg2, db2 = dgrad_bn_bwd(dc3, n, oh, ow, r.w3t, planes, 1, 0, 1, c2, r.st2[0], blk.bn2, grads,
                                  weight=blk.conv3.weight, ctx=f8)
     # configs[4]: e5m2 dc2 (shared with conv2's fp8 dgrad below) x the forward's e4m3 y1
-    w8 = wgrad_f8(f8, q2, dc2, po, 3, blk.conv2.weight, planes) if WGRAD_FP8 else None
+    w8 = wgrad_f8(f8, r.q2, dc2, po, 3, blk.conv2.weight, planes) if WGRAD_FP8 else None
     dw2 = (wgrad if wq is not None else wgrad_now)(
         y1, n, oh, ow, planes, dc2, oh, ow, planes, 3, 1, d, d,
         dw=grads.buf(blk.conv2.weight, planes, 9 * planes), f8=w8)
-    dc1, dg1, db1 = dgrad_bn_bwd(dc2, n, oh, ow, w2t, planes, 3, d, d, c1, st1[0], blk.bn1, grads,
+    dc1, dg1, db1 = dgrad_bn_bwd(dc2, n, oh, ow, r.w2t, planes, 3, d, d, c1, r.st1[0], blk.bn1, grads,
                                  weight=blk.conv2.weight, ctx=f8)
     dw1 = wgrad(x, n, h, w, cin, dc1, oh, ow, planes, 1, s, 0, 1,
                 dw=grads.buf(blk.conv1.weight, planes, cin))
     if need_dx:
-        dx = conv_dgrad(dc1, n, oh, ow, w1t, cin, 1, s, 0, 1, h, w, out=dx, accumulate=dx is not None)
+        dx = conv_dgrad(dc1, n, oh, ow, r.w1t, cin, 1, s, 0, 1, h, w, out=dx, accumulate=dx is not None)
     if has_down:
         dwd = wgrad(x, n, h, w, cin, dcd, oh, ow, 4 * planes, 1, s, 0, 1,
                     dw=grads.buf(blk.downsample[0].weight, 4 * planes, cin))
         grads[blk.downsample[0].weight] = as_param_grad(dwd, blk.downsample[0].weight)
         if need_dx:
-            conv_dgrad(dcd, n, oh, ow, wdt, cin, 1, s, 0, 1, h, w, out=dx, accumulate=True)
+            conv_dgrad(dcd, n, oh, ow, r.wdt, cin, 1, s, 0, 1, h, w, out=dx, accumulate=True)
     grads[blk.conv1.weight] = as_param_grad(dw1, blk.conv1.weight)
     grads[blk.conv2.weight] = as_param_grad(dw2, blk.conv2.weight)
     grads[blk.conv3.weight] = as_param_grad(dw3, blk.conv3.weight)
@@ -435,7 +458,7 @@ def aspp_fwd(mod, x, geo, nseg, rec):
     pool = torch.empty((n, 2048), dtype=dt, device=dev)
     ops.avgpool(x, n, hw, 1.0 / hw, pool)
     wcf, wct = WCACHE.get(mod.conv.weight, dt)
-    cp, _, _, stp = conv_bn(pool, n, 1, 1, wcf, 512, 1, 1, 0, 1, mod.bn_x, tr, nseg, bias=mod.conv.bias)
+    cp, _, _, stp, _ = conv_bn(pool, n, 1, 1, wcf, 512, 1, 1, 0, 1, mod.bn_x, tr, nseg, bias=mod.conv.bias)
     yp = seg_apply(cp, stp, mod.bn_x, act=1)
     nv.call("cn_bcast_rows", ops.dtc(yp), yp.data_ptr(), n, hw, 512, 1.0, cat.data_ptr(), 2560, 0,
             nv.stream())
@@ -448,29 +471,12 @@ def aspp_fwd(mod, x, geo, nseg, rec):
         if qst is not None:
             cat8 = torch.empty((P, 2560), dtype=torch.uint8, device=dev)
             ops.fp8_quant(cat[:, :512], qst, ops.FP8_DELAYED, out=cat8[:, :512])
-    convs = [(mod.conv2d_0, mod.bn_0, 1, 0)] + [
-        (getattr(mod, "conv2d_%d" % (i + 1)), getattr(mod, "bn_%d" % (i + 1)), 3, dd)
-        for i, dd in enumerate(mod.cn_dilations)]
-    # the atrous branches as one grouped launch (train mode, statistics from the epilogue, not
-    # fp8): each branch's launch alone is one round of the chip set by its tiles that skip no tap
-    grouped = {}
-    if (tr and ctx is None and ASPP_GROUPED and fuse_stats(512, 9 * x.shape[1])
-            and all(dd > 0 for (_, _, _, dd) in convs[1:])):
-        at = convs[1:]
-        outs = ops.conv_fwd_bn_grouped(x, n, h, w, [WCACHE.get(cm.weight, dt)[0] for (cm, _, _, _) in at],
-                                       512, 3, [dd for (_, _, _, dd) in at], [bnm for (_, bnm, _, _) in at],
-                                       nseg, biases=[cm.bias for (cm, _, _, _) in at])
-        for bi, (y_, st_) in enumerate(outs):
-            grouped[bi + 1] = (y_, SegStats(st_, nseg, 512))
+    keep8 = rec is not None and WGRAD_FP8
     cs, sts, wts, q8s = [], [], [], []
-    for bi, (cm, bnm, k, dd) in enumerate(convs):
+    for bi, (cm, bnm, k, dd) in enumerate(aspp_branches(mod)):
         wf, wt = WCACHE.get(cm.weight, dt)
-        q = [] if rec is not None and WGRAD_FP8 else None
-        if bi in grouped:
-            ci, st = grouped[bi]
-        else:
-            ci, _, _, st = conv_bn(x, n, h, w, wf, 512, k, 1, dd, max(dd, 1), bnm, tr, nseg, bias=cm.bias,
-                                   weight=cm.weight, q8=q)
+        ci, _, _, st, q = conv_bn(x, n, h, w, wf, 512, k, 1, dd, max(dd, 1), bnm, tr, nseg, bias=cm.bias,
+                                  weight=cm.weight, keep8=keep8)
         q8s.append(q)
         sl = slice(512 * (bi + 1), 512 * (bi + 2))
         if cat8 is not None:
@@ -486,63 +492,60 @@ def aspp_fwd(mod, x, geo, nseg, rec):
     elif ctx is not None:
         ctx.acts.quant(cat, ("cat", id(mod)))   # first use: calibrates the concat's scale
     wbf, wbt = WCACHE.get(mod.bottleneck.weight, dt)
-    qb = [] if rec is not None and WGRAD_FP8 else None
-    cb, _, _, stb = conv_bn(cat, n, h, w, wbf, 256, 3, 1, 1, 1, mod.bn, tr, nseg, bias=mod.bottleneck.bias,
-                            weight=mod.bottleneck.weight, q8=qb)
+    cb, _, _, stb, qb = conv_bn(cat, n, h, w, wbf, 256, 3, 1, 1, 1, mod.bn, tr, nseg, bias=mod.bottleneck.bias,
+                                weight=mod.bottleneck.weight, keep8=keep8)
     out = seg_apply(cb, stb, mod.bn, act=2, prelu=mod.prelu.weight)
     if rec is not None:
-        rec.append(("aspp", mod, (x, pool, cp, yp, stp, wct, cs, sts, wts, cat, cb, stb, wbt, out, q8s, qb),
-                    (n // nseg, h, w, [(k, dd) for (_, _, k, dd) in convs])))
+        rec.append(AsppRec(mod, x, pool, cp, yp, stp, wct, cs, sts, wts, cat, cb, stb, wbt, out, q8s, qb,
+                           n // nseg, h, w))
     return out
 
 
-def aspp_bwd(item, dout, grads):
-    _, mod, sv, (n, h, w, kd) = item
-    x, pool, cp, yp, stp, wct, cs, sts, wts, cat, cb, stb, wbt, out, q8s, qb = sv
+def aspp_bwd(r, dout, grads):
+    mod, n, h, w = r.mod, r.n, r.h, r.w
     hw = h * w
     P = n * hw
     f8 = fp8_of(mod.bn)
     use8 = f8 is not None and WGRAD_FP8
-    x, cat, cb, out = x[:P], cat[:P], cb[:P], out[:P]
-    pool, cp, yp = pool[:n], cp[:n], yp[:n]
+    x, cat, cb, out = r.x[:P], r.cat[:P], r.cb[:P], r.out[:P]
+    pool, cp = r.pool[:n], r.cp[:n]
     pw = mod.prelu.weight
-    dcb, dgb, dbb, dpr = bn_bwd(cb, dout, out, stb[0], mod.bn, act=2, prelu=pw,
+    dcb, dgb, dbb, dpr = bn_bwd(cb, dout, out, r.stb[0], mod.bn, act=2, prelu=pw,
                                 dgamma=grads.buf(mod.bn.weight, 256), dbeta=grads.buf(mod.bn.bias, 256),
                                 dprelu=grads.buf(pw, 1))
     grads[mod.bottleneck.weight] = as_param_grad(
         wgrad_now(cat, n, h, w, 2560, dcb, h, w, 256, 3, 1, 1, 1,
                   dw=grads.buf(mod.bottleneck.weight, 256, 9 * 2560),
-                  f8=wgrad_f8(f8, qb, dcb, P, 3, mod.bottleneck.weight, 2560) if use8 else None),
+                  f8=wgrad_f8(f8, r.qb, dcb, P, 3, mod.bottleneck.weight, 2560) if use8 else None),
         mod.bottleneck.weight)
     grads[mod.bottleneck.bias] = ops.colsum(dcb, out=grads.buf(mod.bottleneck.bias, 256))
     grads[mod.bn.weight], grads[mod.bn.bias], grads[pw] = dgb, dbb, dpr
-    dcat = dgrad(dcb, n, h, w, wbt, 2560, 3, 1, 1, h, w, mod.bottleneck.weight, f8)
+    dcat = dgrad(dcb, n, h, w, r.wbt, 2560, 3, 1, 1, h, w, mod.bottleneck.weight, f8)
     dx = None
-    bns = [mod.bn_0, mod.bn_1, mod.bn_2, mod.bn_3]
-    cms = [mod.conv2d_0, mod.conv2d_1, mod.conv2d_2, mod.conv2d_3]
-    for bi, ((k, dd), ci, st, wt) in enumerate(zip(kd, cs, sts, wts)):
+    saved = zip(aspp_branches(mod), r.cs, r.sts, r.wts, r.q8s)
+    for bi, ((cm, bnm, k, dd), ci, st, wt, q) in enumerate(saved):
         sl = slice(512 * (bi + 1), 512 * (bi + 2))
-        dci, dgi, dbi, _ = bn_bwd(ci[:P], dcat[:, sl], None, st[0], bns[bi], act=1,
-                                  dgamma=grads.buf(bns[bi].weight, 512), dbeta=grads.buf(bns[bi].bias, 512))
-        grads[cms[bi].weight] = as_param_grad(
+        dci, dgi, dbi, _ = bn_bwd(ci[:P], dcat[:, sl], None, st[0], bnm, act=1,
+                                  dgamma=grads.buf(bnm.weight, 512), dbeta=grads.buf(bnm.bias, 512))
+        grads[cm.weight] = as_param_grad(
             wgrad_now(x, n, h, w, 2048, dci, h, w, 512, k, 1, dd, max(dd, 1),
-                      dw=grads.buf(cms[bi].weight, 512, k * k * 2048),
-                      f8=wgrad_f8(f8, q8s[bi], dci, P, k, cms[bi].weight, 2048) if use8 else None),
-            cms[bi].weight)
-        grads[cms[bi].bias] = ops.colsum(dci, out=grads.buf(cms[bi].bias, 512))
-        grads[bns[bi].weight], grads[bns[bi].bias] = dgi, dbi
-        dx = dgrad(dci, n, h, w, wt, 2048, k, dd, max(dd, 1), h, w, cms[bi].weight, f8, out=dx,
+                      dw=grads.buf(cm.weight, 512, k * k * 2048),
+                      f8=wgrad_f8(f8, q, dci, P, k, cm.weight, 2048) if use8 else None),
+            cm.weight)
+        grads[cm.bias] = ops.colsum(dci, out=grads.buf(cm.bias, 512))
+        grads[bnm.weight], grads[bnm.bias] = dgi, dbi
+        dx = dgrad(dci, n, h, w, wt, 2048, k, dd, max(dd, 1), h, w, cm.weight, f8, out=dx,
                    accumulate=dx is not None)
     dyp = torch.empty((n, 512), dtype=dout.dtype, device=dout.device)
     ops.avgpool(dcat[:, :512], n, hw, 1.0, dyp)
-    dcp, dgx, dbx, _ = bn_bwd(cp, dyp, None, stp[0], mod.bn_x, act=1,
+    dcp, dgx, dbx, _ = bn_bwd(cp, dyp, None, r.stp[0], mod.bn_x, act=1,
                               dgamma=grads.buf(mod.bn_x.weight, 512), dbeta=grads.buf(mod.bn_x.bias, 512))
     grads[mod.conv.weight] = as_param_grad(conv_wgrad(pool, n, 1, 1, 2048, dcp, 1, 1, 512, 1, 1, 0, 1,
                                                       dw=grads.buf(mod.conv.weight, 512, 2048)),
                                            mod.conv.weight)
     grads[mod.conv.bias] = ops.colsum(dcp, out=grads.buf(mod.conv.bias, 512))
     grads[mod.bn_x.weight], grads[mod.bn_x.bias] = dgx, dbx
-    dpool = conv_dgrad(dcp, n, 1, 1, wct, 2048, 1, 1, 0, 1, 1, 1)
+    dpool = conv_dgrad(dcp, n, 1, 1, r.wct, 2048, 1, 1, 0, 1, 1, 1)
     nv.call("cn_bcast_rows", ops.dtc(dpool), dpool.data_ptr(), n, hw, 2048, 1.0 / hw,
             dx.data_ptr(), ops.ld(dx), 1, nv.stream())
     return dx
@@ -562,9 +565,8 @@ class EncoderPairFn(F):
         if fp8 is not None:
             fp8.acts.begin()
         x, geo = stem_fwd(enc.backbone, (img_a, img_b), nseg, dt, rec)
-        for layer in (enc.backbone.layer1, enc.backbone.layer2, enc.backbone.layer3, enc.backbone.layer4):
-            for blk in layer:
-                x, geo = bottleneck_fwd(blk, x, geo, nseg, rec)
+        for blk in blocks(enc):
+            x, geo = bottleneck_fwd(blk, x, geo, nseg, rec)
         out = aspp_fwd(enc.aspp, x, geo, nseg, rec)
         if fp8 is not None:
             fp8.acts.end()
@@ -599,18 +601,16 @@ class EncoderPairFn(F):
             f8.grads.begin()
         wq = WgradQueue()
         dx = aspp_bwd(rec.pop(), dfa, grads)
-        stem = rec[0]
-        blocks = rec[1:]
-        del rec[:]                         # each block's saved tensors die with its backward
-        layer_of = _layer_index(ctx.enc)
-        while blocks:
-            item = blocks.pop()
-            dx = bottleneck_bwd(item, dx, grads, wq=wq)
+        stem = rec.pop(0)
+        layer = layer_of(ctx.enc)
+        while rec:                         # each block's saved tensors die with its backward
+            r = rec.pop()
+            dx = bottleneck_bwd(r, dx, grads, wq=wq)
             # WGRAD_FLUSH "layer": issue the queued weight gradients after the last (first in
             # backward order) block of each layer, releasing their dY / input tensors there
-            if WGRAD_FLUSH == "layer" and (not blocks or layer_of[id(blocks[-1][1])] != layer_of[id(item[1])]):
+            if WGRAD_FLUSH == "layer" and (not rec or layer[rec[-1].mod] != layer[r.mod]):
                 wq.flush()
-            del item
+            del r
         stem_bwd(stem, dx, grads)
         wq.flush()
         if f8 is not None:
@@ -631,46 +631,38 @@ class DeferredEncoderBwd:
         self.enc = enc
         self.arena = arena
         self.rec = self.dfa = self.dx = None
-        bb = enc.backbone
-        l3 = list(bb.layer3)
-        l3_rev = list(reversed(l3))
-        if len(l3) > 10:
-            h = len(l3) // 2
-            mid = [l3_rev[:h], l3_rev[h:]]
-        else:
-            mid = [l3_rev]
-        # each segment: list of ("aspp" | block | "stem") in backward order
-        self.plan = ([["aspp"] + list(reversed(list(bb.layer4)))] + mid +
-                     [list(reversed(list(bb.layer2))) + list(reversed(list(bb.layer1))) + ["stem"]])
+        l1, l2, l3, l4 = (list(reversed(layer)) for layer in layers(enc))
+        mid = [l3[:len(l3) // 2], l3[len(l3) // 2:]] if len(l3) > 10 else [l3]
+        # each segment: the modules whose records it runs (the ASPP, blocks, the backbone for the
+        # stem) in backward order
+        self.plan = [[enc.aspp] + l4] + mid + [l2 + l1 + [enc.backbone]]
 
     def segment_params(self, k):
         """Parameters whose gradients segment k produces (its bucket), in production order."""
         out = []
-        for it in self.plan[k]:
-            mod = self.enc.aspp if it == "aspp" else (self.enc.backbone if it == "stem" else it)
-            if it == "stem":
+        for mod in self.plan[k]:
+            if mod is self.enc.backbone:
                 out += [mod.conv1.weight, mod.bn1.weight, mod.bn1.bias]
             else:
                 out += [p for p in mod.parameters() if p.requires_grad]
         return out
 
     def stash(self, rec, dfa):
-        self.rec, self.dfa = rec, dfa
+        self.rec, self.dfa = {r.mod: r for r in rec}, dfa
 
     def run(self, k):
         rec, grads = self.rec, GradSink(self.arena)
-        by_blk = {it[1]: it for it in rec[1:-1]}
         f8 = getattr(self.enc, "_cn_fp8", None)
         if f8 is not None and k == 0:
             f8.grads.begin()
         wq = WgradQueue()     # the segment's weight gradients, grouped at its end (its bucket)
-        for it in self.plan[k]:
-            if it == "aspp":
-                self.dx = aspp_bwd(rec[-1], self.dfa, grads)
-            elif it == "stem":
-                stem_bwd(rec[0], self.dx, grads)
+        for mod in self.plan[k]:
+            if mod is self.enc.aspp:
+                self.dx = aspp_bwd(rec[mod], self.dfa, grads)
+            elif mod is self.enc.backbone:
+                stem_bwd(rec[mod], self.dx, grads)
             else:
-                self.dx = bottleneck_bwd(by_blk[it], self.dx, grads, wq=wq)
+                self.dx = bottleneck_bwd(rec[mod], self.dx, grads, wq=wq)
         wq.flush()
         if k == len(self.plan) - 1:
             self.rec = self.dfa = self.dx = None

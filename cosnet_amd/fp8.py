@@ -25,6 +25,7 @@ bf16 path.
   operands k-major through ds_read_b64_tr_b8; the bottlenecks' 3x3 convs grouped per layer like
   the bf16 ones.  The 1x1 / shallow weight gradients (no e5m2 dY) stay bf16 x bf16.
 """
+import collections
 import struct
 import weakref
 
@@ -40,6 +41,24 @@ assert _REC.size == 56
 
 def fp8_ok(x, cin):
     return x.dtype == torch.bfloat16 and cin % 16 == 0 and ops.ld(x) % 16 == 0
+
+
+FP8_MIN_ROWS = 64   # a conv of at most this many input rows keeps its bf16 operands
+
+
+def fp8_rows_ok(rows):
+    return rows > FP8_MIN_ROWS
+
+
+def fp8_conv_ok(x, cin):
+    """Does a conv of cin input channels reading x [rows][cin] run its forward in fp8: the e4m3
+    layout (fp8_ok) and enough rows.  The one rule of the training path (conv_bn; fp8_dgrad_ok
+    for the output gradient a dgrad reads) and of the static walk (fp8_infer), which tests its
+    two halves up front: the layout on the stem output, the rows on its smallest map."""
+    return fp8_ok(x, cin) and fp8_rows_ok(x.shape[0])
+
+
+Saved8 = collections.namedtuple("Saved8", "x8 handle slot")   # Fp8Acts.saved()
 
 
 class Fp8Weights:
@@ -166,9 +185,9 @@ class Fp8Acts:
         return (st.data_ptr() - self.states.data_ptr()) // (4 * self.states.element_size())
 
     def saved(self, x8, st):
-        """(x8, pass handle, slot): what a backward needs to dequantise x8 after end() advanced
+        """Saved8(x8, pass handle, slot): what a backward needs to dequantise x8 after end() advanced
         the live scale -- the handle's snapshot holds the scale x8 was quantised with."""
-        return (x8, self.handle, self.slot_of(st))
+        return Saved8(x8, self.handle, self.slot_of(st))
 
     def begin(self):
         self.pass_cache = {}

@@ -14,13 +14,13 @@ Here the scales are calibrated once and frozen:
   (scale = amax * margin / 448 by cn_fp8_update, as the delayed path computes it) and quantises
   every eligible conv weight once with current scaling.
 * encode_frames_static() walks one encoder in the layer order of EncoderPairFn.forward (one
-  segment, running statistics).  Every eligible conv -- the convs conv_bn would run in fp8:
-  fp8_ok(x, cin) and more than 64 rows -- is cn_conv_fwd_fp8 on an e4m3 image written by its
-  producer's cn_bn_apply_q8 (the stem / maxpool output and the pooled rows of the ASPP concat,
-  which no BN apply produces, by cn_fp8_quant_static).  A bottleneck's y1 and y2 and the ASPP's
-  2560-wide concat exist as e4m3 only; block outputs as bf16 (the residual) and e4m3.  No launch
-  of the walk writes a scale state, so a frame's features depend on the frame, the weights and
-  the calibration alone.
+  segment, running statistics).  Every eligible conv -- the convs conv_bn would run in fp8, by
+  fp8.fp8_conv_ok: a bf16 input of 16-channel multiples and more than FP8_MIN_ROWS rows -- is
+  cn_conv_fwd_fp8 on an e4m3 image written by its producer's cn_bn_apply_q8 (the stem / maxpool
+  output and the pooled rows of the ASPP concat, which no BN apply produces, by
+  cn_fp8_quant_static).  A bottleneck's y1 and y2 and the ASPP's 2560-wide concat exist as e4m3
+  only; block outputs as bf16 (the residual) and e4m3.  No launch of the walk writes a scale
+  state, so a frame's features depend on the frame, the weights and the calibration alone.
 
 One state per tensor: a block's input, read by its conv1 and its downsample conv, has one
 ("<block>.x"); so have its y1 and y2, the ASPP's input ("aspp.x") and the whole concat
@@ -33,18 +33,12 @@ import torch
 
 from . import encoder_fn as E
 from . import ops
-from .fp8 import Fp8Weights, fp8_ok
+from .fp8 import FP8_MIN_ROWS, Fp8Weights, fp8_ok, fp8_rows_ok
 from .ops import WCACHE
 
 FORMAT = "cosnet_amd.fp8_calibration"
 FORMAT_VERSION = 1
 ENCODERS = ("encoder", "depth_encoder")
-MIN_ROWS = 64   # conv_bn runs a conv in fp8 above this many input rows
-
-
-def _blocks(enc):
-    bb = enc.backbone
-    return [blk for layer in (bb.layer1, bb.layer2, bb.layer3, bb.layer4) for blk in layer]
 
 
 def _paths(enc):
@@ -56,25 +50,19 @@ def state_names(enc):
     """The names of one encoder's fp8 activation states, in walk order."""
     paths = _paths(enc)
     names = []
-    for blk in _blocks(enc):
+    for blk in E.blocks(enc):
         names += [paths[id(blk)] + s for s in (".x", ".y1", ".y2")]
     return names + [paths[id(enc.aspp)] + ".x", paths[id(enc.aspp)] + ".cat"]
-
-
-def _aspp_convs(mod):
-    return [(mod.conv2d_0, mod.bn_0, 1, 0)] + [
-        (getattr(mod, "conv2d_%d" % (i + 1)), getattr(mod, "bn_%d" % (i + 1)), 3, dd)
-        for i, dd in enumerate(mod.cn_dilations)]
 
 
 def fp8_conv_weights(enc):
     """The weights of the convs the static walk runs in fp8."""
     ws = []
-    for blk in _blocks(enc):
+    for blk in E.blocks(enc):
         ws += [blk.conv1.weight, blk.conv2.weight, blk.conv3.weight]
         if blk.downsample is not None:
             ws.append(blk.downsample[0].weight)
-    ws += [cm.weight for cm, _, _, _ in _aspp_convs(enc.aspp)] + [enc.aspp.bottleneck.weight]
+    ws += [cm.weight for cm, _, _, _ in E.aspp_branches(enc.aspp)] + [enc.aspp.bottleneck.weight]
     return ws
 
 
@@ -143,19 +131,19 @@ def _calib_walk(enc, imgs, states, slot):
 
     with E.no_fp8():
         x, geo = E.stem_fwd(enc.backbone, (imgs,), 1, dt, None)
-        for blk in _blocks(enc):
+        for blk in E.blocks(enc):
             name = paths[id(blk)]
             rec = []
             amax(x, name + ".x")
             x, geo = E.bottleneck_fwd(blk, x, geo, 1, rec)
-            sv = rec[0][2]
-            amax(sv[2], name + ".y1")
-            amax(sv[4], name + ".y2")
+            r = rec.pop()
+            amax(r.y1, name + ".y1")
+            amax(r.y2, name + ".y2")
         name = paths[id(enc.aspp)]
         amax(x, name + ".x")
         rec = []
         E.aspp_fwd(enc.aspp, x, geo, 1, rec)
-        amax(rec[0][2][9], name + ".cat")
+        amax(rec.pop().cat, name + ".cat")
 
 
 @torch.no_grad()
@@ -201,7 +189,7 @@ class EncoderStatic:
         ops.fp8_update(self.states, margin)
         self.weights = Fp8Weights()
         for w in fp8_conv_weights(enc):
-            if w.shape[1] % 16:
+            if w.shape[1] % 16:   # fp8_ok's channel rule, known before any frame arrives
                 raise ValueError("static fp8: a conv of %d input channels cannot take fp8 operands"
                                  % w.shape[1])
             self.weights.get(w)   # quantised now: nothing is calibrated on first use
@@ -275,7 +263,7 @@ def aspp_static(mod, x, x8, geo, S):
     yp = ops.bn_apply(cp, _eval_stats(cp, mod.bn_x), mod.bn_x, act=1)
     cat8 = torch.empty((P, 2560), dtype=torch.uint8, device=x.device)
     ops.bcast_rows_u8(ops.fp8_quant_static(yp, sc), n, hw, cat8[:, :512])
-    for bi, (cm, bnm, k, dd) in enumerate(_aspp_convs(mod)):
+    for bi, (cm, bnm, k, dd) in enumerate(E.aspp_branches(mod)):
         w8, ws = S.w8(cm.weight)
         ci, _, _ = ops.conv_fwd_fp8(x8, n, h, w, w8, 512, k, 1, dd, max(dd, 1), sx, ws, bias=cm.bias)
         ops.bn_apply_q8(ci, _eval_stats(ci, bnm), bnm, sc, act=1,
@@ -298,10 +286,10 @@ def encode_frames_static(enc, imgs):
         x, geo = E.stem_fwd(enc.backbone, (imgs,), 1, dt, None)
     n, h, w = geo
     fh, fw = ops.out_hw(h, w, 1, 2, 0, 1)   # layer2's stride; layers 3-4 keep the size
-    if n * fh * fw <= MIN_ROWS:
+    if not fp8_rows_ok(n * fh * fw):
         raise ValueError("static fp8: %d feature-map rows; the fp8 convs need more than %d"
-                         % (n * fh * fw, MIN_ROWS))
-    blocks = _blocks(enc)
+                         % (n * fh * fw, FP8_MIN_ROWS))
+    blocks = E.blocks(enc)
     if not fp8_ok(x, x.shape[1]):
         raise RuntimeError("static fp8: the stem output cannot take the fp8 layout")
     x8 = ops.fp8_quant_static(x, S.st(S.paths[id(blocks[0])] + ".x"))

@@ -846,6 +846,18 @@ def relu_mask(p, c, like):
     return torch.empty((p, c // vec), dtype=torch.uint8, device=like.device)
 
 
+def _bn_apply_args(x, stats, bn, act, prelu, res, xr, rstats, rbn, nseg):
+    """The arguments cn_bn_apply_ex and cn_bn_apply_q8 share, dtype to prelu: each wrapper appends
+    its outputs."""
+    p, c = x.shape
+    g, b = _affine(bn)
+    rg, rb = _affine(rbn) if rbn is not None else (None, None)
+    return (dtc(x), x.data_ptr(), ld(x), p // nseg, nseg, c, stats[0].data_ptr(), stats[1].data_ptr(),
+            nv.ptr(g), nv.ptr(b), nv.ptr(res), ld(res) if res is not None else 0,
+            nv.ptr(xr), ld(xr) if xr is not None else 0, nv.ptr(rstats[0] if rstats else None),
+            nv.ptr(rstats[1] if rstats else None), nv.ptr(rg), nv.ptr(rb), act, nv.ptr(prelu))
+
+
 def bn_apply(x, stats, bn, act=0, prelu=None, res=None, xr=None, rstats=None, rbn=None, out=None,
              nseg=1, out8=None, qstate=None, mask=None):
     """y = act(bn(x) [+ res] [+ rbn(xr)]) with per-segment statistics ([nseg*C] each); with
@@ -855,15 +867,9 @@ def bn_apply(x, stats, bn, act=0, prelu=None, res=None, xr=None, rstats=None, rb
     The fp8 copy (bf16 only; out8 row stride a multiple of 16) is quantised from the fp32 value of
     the activation BEFORE its rounding to bf16: out8 = e4m3(clamp(t * qstate[1], +-448)) and
     qstate[2] = max |t| with t the fp32 activation, so out8 is not the quantised stored y."""
-    p, c = x.shape
     if out is None:
-        out = torch.empty((p, c), dtype=x.dtype, device=x.device)
-    g, b = _affine(bn)
-    rg, rb = _affine(rbn) if rbn is not None else (None, None)
-    nv.call("cn_bn_apply_ex", dtc(x), x.data_ptr(), ld(x), p // nseg, nseg, c, stats[0].data_ptr(),
-            stats[1].data_ptr(), nv.ptr(g), nv.ptr(b), nv.ptr(res), ld(res) if res is not None else 0,
-            nv.ptr(xr), ld(xr) if xr is not None else 0, nv.ptr(rstats[0] if rstats else None),
-            nv.ptr(rstats[1] if rstats else None), nv.ptr(rg), nv.ptr(rb), act, nv.ptr(prelu),
+        out = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
+    nv.call("cn_bn_apply_ex", *_bn_apply_args(x, stats, bn, act, prelu, res, xr, rstats, rbn, nseg),
             out.data_ptr(), ld(out), nv.ptr(out8), ld(out8) if out8 is not None else 0,
             nv.ptr(qstate), nv.ptr(mask), mask.stride(0) if mask is not None else 0, nv.stream())
     return out
@@ -874,15 +880,9 @@ def bn_apply_q8(x, stats, bn, qstate, act=0, prelu=None, res=None, xr=None, rsta
     """bn_apply whose e4m3 image out8 is written under the frozen, read-only qstate
     (cn_bn_apply_q8: no amax, nothing written to qstate); the bf16 output only into a given
     `out`.  Returns (out or None, out8)."""
-    p, c = x.shape
     if out8 is None:
-        out8 = torch.empty((p, c), dtype=torch.uint8, device=x.device)
-    g, b = _affine(bn)
-    rg, rb = _affine(rbn) if rbn is not None else (None, None)
-    nv.call("cn_bn_apply_q8", dtc(x), x.data_ptr(), ld(x), p // nseg, nseg, c, stats[0].data_ptr(),
-            stats[1].data_ptr(), nv.ptr(g), nv.ptr(b), nv.ptr(res), ld(res) if res is not None else 0,
-            nv.ptr(xr), ld(xr) if xr is not None else 0, nv.ptr(rstats[0] if rstats else None),
-            nv.ptr(rstats[1] if rstats else None), nv.ptr(rg), nv.ptr(rb), act, nv.ptr(prelu),
+        out8 = torch.empty(tuple(x.shape), dtype=torch.uint8, device=x.device)
+    nv.call("cn_bn_apply_q8", *_bn_apply_args(x, stats, bn, act, prelu, res, xr, rstats, rbn, nseg),
             nv.ptr(out), ld(out) if out is not None else 0, out8.data_ptr(), ld(out8),
             qstate.data_ptr(), nv.stream())
     return out, out8

@@ -140,8 +140,8 @@ def test_fp8_weight_gradient_of_bottleneck_matches_its_operands(cuda, monkeypatc
     wq.flush()
     torch.cuda.synchronize()
     dw2 = grads[blk.conv2.weight].detach().double().cpu()
-    x8, handle, slot = rec[0][2][16][0]          # conv2's saved e4m3 input (Fp8Acts.saved)
-    sx = handle.state(slot)[0].item()
+    q2 = rec[0].q2                               # conv2's saved e4m3 input (Fp8Acts.saved)
+    x8, sx = q2.x8, q2.handle.state(q2.slot)[0].item()
     dys = [v for v in ctx.grads.pass_cache.values() if tuple(v[0].shape) == (n1 * h * w, 256)]
     assert len(dys) == 1, [tuple(v[0].shape) for v in ctx.grads.pass_cache.values()]
     dy8, ds = dys[0][0], dys[0][1][0].item()
@@ -158,7 +158,7 @@ def test_fp8_weight_gradient_of_bottleneck_matches_its_operands(cuda, monkeypatc
     err = ((dw2 - ref).abs().max() / ref.abs().max()).item()
     assert err <= 2e-3, err
     # the same backward's bf16 operands: y1 (frame a) and dc2 (the tensor dy8 quantises)
-    y1 = rec[0][2][2][:n1 * h * w]
+    y1 = rec[0].y1[:n1 * h * w]
     ref16 = wgrad64(y1.double().cpu().view(n1, h, w, 256), dys[0][2].double().cpu())
     qerr = ((ref - ref16).norm() / ref16.norm()).item()
     assert 0 < qerr <= 0.15, qerr
@@ -208,15 +208,14 @@ def test_fp8_vs_bf16_weight_gradient_with_pinned_scales(cuda, monkeypatch):
         torch.cuda.synchronize()
         dys = [v for v in ctx.grads.pass_cache.values() if tuple(v[0].shape) == (n1 * h * w, 256)]
         assert len(dys) == 1
-        out[on] = (grads[blk.conv2.weight].detach().double().cpu(), rec[0][2][2][:n1 * h * w].clone(),
-                   dys[0][2].clone(), rec[0][2][16][0] if on else None, dys[0][0].clone(),
+        out[on] = (grads[blk.conv2.weight].detach().double().cpu(), rec[0].y1[:n1 * h * w].clone(),
+                   dys[0][2].clone(), rec[0].q2 if on else None, dys[0][0].clone(),
                    dys[0][1][0].item())
         ctx.grads.end()
     (dw8, y1a, dca, q2, dy8, ds), (dw16, y1b, dcb, _, _, _) = out[True], out[False]
     # the pinned scales reproduce the forward and the dgrad chain bit for bit
     assert torch.equal(y1a, y1b) and torch.equal(dca, dcb)
-    x8, handle, slot = q2
-    sx = handle.state(slot)[0].item()
+    x8, sx = q2.x8, q2.handle.state(q2.slot)[0].item()
 
     def wgrad64(xa, da):
         xp = torch.nn.functional.pad(xa, (0, 0, 2, 2, 2, 2))

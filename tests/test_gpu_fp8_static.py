@@ -20,6 +20,7 @@ import torch
 
 from conftest import golden
 import cosnet_amd as C
+from cosnet_amd import encoder_fn as E
 from cosnet_amd import fp8_infer as FI
 from cosnet_amd import ops
 from cosnet_amd.inference import FeatureBank, multi_reference_x1, segment_sequence
@@ -103,8 +104,24 @@ def test_calibration_is_a_function_of_the_frame_set(cuda, bf16_model, tmp_path):
     assert c1 == c4 == cr
     with torch.no_grad():
         m._set_dtype()
-        z, _ = m.encoder.backbone.forward_nhwc(m._prep(rgbs))
+        z, zgeo = m.encoder.backbone.forward_nhwc(m._prep(rgbs))
     assert c4.amax["encoder"]["aspp.x"] == z.float().abs().max().item()
+    # the tensors the walk takes from the forward's records: a block with a downsample, one
+    # without, and the ASPP's concat, against the block functions run here.  Exact: the amax is an
+    # integer atomic max on the float bits and eval-mode BN makes every tensor independent of chunking
+    enc, amax = m.encoder, c4.amax["encoder"]
+    with torch.no_grad(), E.no_fp8():
+        x, geo = E.stem_fwd(enc.backbone, (m._prep(rgbs),), 1, torch.bfloat16, None)
+        for i in (0, 1):
+            rec = []
+            x, geo = E.bottleneck_fwd(enc.backbone.layer1[i], x, geo, 1, rec)
+            assert (enc.backbone.layer1[i].downsample is not None) == (i == 0)
+            for f in ("y1", "y2"):
+                assert amax["backbone.layer1.%d.%s" % (i, f)] == float(getattr(rec[0], f).float().abs().max())
+        rec = []
+        E.aspp_fwd(enc.aspp, z, zgeo, 1, rec)
+        assert zgeo == (4, 9, 11)
+        assert amax["aspp.cat"] == float(rec[0].cat.float().abs().max())
     # the tables built from them
     ms = make_model(cuda, torch.bfloat16)
     t1 = [t.clone() for t in tables(ms.set_fp8_static(c1))]

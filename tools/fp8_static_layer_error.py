@@ -60,7 +60,7 @@ def main():
     for key, imgs in (("encoder", rgbs), ("depth_encoder", deps)):
         enc = getattr(m, key)
         S = enc._cn_fp8_static
-        blocks = FI._blocks(enc)
+        blocks = E.blocks(enc)
         with torch.no_grad(), E.no_fp8():
             xb, geo = E.stem_fwd(enc.backbone, (imgs,), 1, torch.bfloat16, None)
             xs, gs = xb, geo

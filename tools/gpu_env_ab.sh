@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box A/B of an environment switch on the default bench line (no CPU baseline):
-#   bash tools/gpu_env_ab.sh TAG "ENV_A" "ENV_B" [reps]   e.g. "CN_ASPP_GROUPED=1" "CN_ASPP_GROUPED=0"
+#   bash tools/gpu_env_ab.sh TAG "ENV_A" "ENV_B" [reps]   e.g. "CN_WGRAD_FLUSH=layer" "CN_WGRAD_FLUSH=end"
 set -o pipefail
 TAG=$1; A=$2; B=$3; R=${4:-2}
 O=gpurun_out/envab_$TAG
