@@ -6,6 +6,7 @@ the library is loaded so that both share torch's HIP runtime (same soname).
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (loads the HIP runtime the library binds to)
 
@@ -16,132 +17,54 @@ LIB_PATH = os.environ.get("COSNET_HIP_LIB") or os.path.join(_HERE, "_lib", "libc
 DT_F32 = 0
 DT_BF16 = 1
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_L = ctypes.c_longlong
-_F = ctypes.c_float
-_S = ctypes.c_size_t
-
-# name -> (restype, argtypes); stream is always the last argument (void*)
-_SIGS = {
-    "cn_conv_fwd": (_I, [_I, _P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _L, _I, _I, _P]),
-    "cn_conv_fwd_ws": (_I, [_I, _P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _L, _I, _I,
-                            _P, _S, _P]),
-    "cn_conv_fwd_workspace_floats": (_S, [_I, _I, _I, _I]),
-    "cn_conv_dgrad": (_I, [_I, _P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _L, _I, _I, _I, _P]),
-    "cn_conv_wgrad_workspace_floats": (_S, [_I, _I, _I, _I, _I, _I, _I, _I]),
-    "cn_conv_wgrad": (_I, [_I, _P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "cn_conv_wgrad_grouped": (_I, [_I, _I, _P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I,
-                                   _P, _P]),
-    "cn_conv_wgrad_grouped_workspace_floats": (_S, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
-    "cn_conv_wgrad_grouped_ws": (_I, [_I, _I, _P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _I, _I, _I, _I,
-                                      _I, _P, _P, _S, _P]),
-    "cn_splitk_reduce": (_I, [_P, _I, _L, _L, _P, _I, _P]),
-    "cn_fp8_quant": (_I, [_I, _P, _L, _I, _I, _P, _L, _P, _I, _P]),
-    "cn_fp8_quant_fmt": (_I, [_I, _I, _P, _L, _I, _I, _P, _L, _P, _I, _P]),
-    "cn_conv_dgrad_fp8": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _L, _I, _I, _I,
-                               _P, _P, _P]),
-    "cn_fp8_update": (_I, [_P, _I, _F, _P]),
-    "cn_fp8_quant_multi": (_I, [_P, _I, _P]),
-    "cn_conv_fwd_fp8": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _L, _I, _I, _P,
-                             _P, _P]),
-    "cn_conv_fwd_bn_workspace_floats": (_S, [_I, _I, _I, _I]),
-    "cn_conv_fwd_bn_grouped": (_I, [_I, _P, _L, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _L, _I,
-                                    _P, _P, _P, _P, _P, _F, _F, _P]),
-    "cn_conv_fwd_fp8_bn": (_I, [_P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _L, _I, _I,
-                                _P, _P, _I, _P, _P, _P, _P, _P, _F, _F, _P]),
-    "cn_conv_fwd_bn": (_I, [_I, _P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _L, _I, _I,
-                            _I, _P, _P, _P, _P, _P, _F, _F, _P]),
-    "cn_conv_dgrad_bn_workspace_floats": (_S, [_I, _I, _I, _I]),
-    "cn_conv_dgrad_bn": (_I, [_I, _P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _L, _I, _I, _P,
-                              _L, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "cn_bn_bwd_apply": (_I, [_I, _P, _L, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
-    "cn_gemm": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _F, _P, _I, _I, _L, _P]),
-    "cn_bn_workspace_floats": (_S, [_I, _I, _I, _I]),
-    "cn_bn_stats": (_I, [_I, _P, _L, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P]),
-    "cn_bn_eval_params": (_I, [_P, _P, _I, _F, _P, _P, _P]),
-    "cn_bn_apply": (_I, [_I, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P, _P, _L, _P]),
-    "cn_bn_apply_fp8": (_I, [_I, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P,
-                             _P, _L, _P, _L, _P, _P]),
-    "cn_bn_apply_ex": (_I, [_I, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P,
-                            _P, _L, _P, _L, _P, _P, _L, _P]),
-    "cn_bn_apply_q8": (_I, [_I, _P, _L, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _I, _P,
-                            _P, _L, _P, _L, _P, _P]),
-    "cn_fp8_quant_static": (_I, [_I, _I, _P, _L, _I, _I, _P, _L, _P, _P]),
-    "cn_bcast_rows_u8": (_I, [_P, _I, _I, _I, _P, _L, _P]),
-    "cn_bn_set_tuning": (_I, [_I, _I]),
-    "cn_bn_bwd": (_I, [_I, _P, _L, _P, _L, _P, _L, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P]),
-    "cn_coatt_workspace_floats": (_S, [_I, _I, _I]),
-    "cn_coatt_softmax": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "cn_coatt_dscore": (_I, [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
-    "cn_coatt_fused_fwd": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P]),
-    "cn_coatt_fused_fwd_ws": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _S, _P]),
-    "cn_coatt_fused_workspace_bytes": (_S, [_I, _I, _I]),
-    "cn_coatt_fused_fwd_idx": (_I, [_P, _L, _P, _L, _P, _L, _P, _P, _I, _I, _I, _P, _P, _L, _P, _S, _P]),
-    "cn_gate_cat_idx": (_I, [_I, _P, _L, _P, _L, _P, _I, _I, _I, _P, _P, _P, _L, _P]),
-    "cn_mean_groups": (_I, [_P, _I, _I, _I, _P, _P]),
-    "cn_coatt_f8_workspace_bytes": (_S, [_I, _I]),
-    "cn_coatt_f8_fwd": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _P, _P, _S, _P]),
-    "cn_coatt_f8_train_workspace_bytes": (_S, [_I, _I]),
-    "cn_coatt_f8_train_fwd": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P, _L, _P, _S, _P]),
-    "cn_coatt_f8_bank_bytes": (_S, [_I, _I]),
-    "cn_coatt_f8_bank_build": (_I, [_P, _L, _P, _L, _I, _I, _I, _P, _S, _P]),
-    "cn_coatt_f8_fwd_idx": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _L, _P]),
-    "cn_coatt_flash_fwd": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _P, _P]),
-    "cn_coatt_flash_fwd_ws": (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _P, _P, _L, _P, _P, _P, _S, _P]),
-    "cn_coatt_flash_pv": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _I, _P]),
-    "cn_coatt_flash_dvat": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _I, _I, _I, _P,
-                                 _L, _I, _P]),
-    "cn_coatt_flash_dvat_ws": (_I, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _P, _P, _P, _I, _I, _I, _P,
-                                    _L, _I, _P, _S, _P]),
-    "cn_coatt_flash_bwd_workspace_bytes": (_S, [_I, _I]),
-    "cn_coatt_flash_pv_ws": (_I, [_P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _P, _L, _I, _P, _S, _P]),
-    "cn_rowdot_seg": (_I, [_I, _P, _L, _P, _L, _I, _I, _I, _I, _P, _P]),
-    "cn_nchw_to_nhwc": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "cn_weight_prep": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "cn_maxpool_fwd": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "cn_maxpool_bwd": (_I, [_I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cn_avgpool": (_I, [_I, _P, _L, _I, _I, _I, _F, _P, _P, _P]),
-    "cn_avgpool_workspace_floats": (_S, [_I, _I, _I, _I]),
-    "cn_bcast_rows": (_I, [_I, _P, _I, _I, _I, _F, _P, _L, _I, _P]),
-    "cn_gate_fwd": (_I, [_I, _P, _L, _I, _I, _P, _P, _P, _L, _P, _P]),
-    "cn_gate_bwd": (_I, [_I, _P, _L, _P, _L, _P, _I, _I, _P, _I, _P, _L, _P, _P, _P, _P]),
-    "cn_colpart_workspace_floats": (_S, [_I, _I]),
-    "cn_mean_rows": (_I, [_P, _I, _I, _P, _P]),
-    "cn_sum_rows": (_I, [_P, _I, _I, _P, _P]),
-    "cn_scale_dev": (_I, [_P, _L, _P, _P, _P]),
-    "cn_scale": (_I, [_P, _L, _F, _P]),
-    "cn_soft_iou": (_I, [_P, _P, _I, _L, _P, _P, _P, _P]),
-    "cn_frame_resize": (_I, [_I, _P, _I, _L, _L, _L, _I, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
-    "cn_gemm_force_config": (_I, [_I]),
-    "cn_gemm_ws_mode": (_I, [_I]),
-    "cn_gemm_ws_launches": (_S, []),
-    "cn_gemm_set_wgrad_target": (_I, [_I]),
-    "cn_coatt_force_variant": (_I, [_I]),
-    "cn_head_fwd": (_I, [_I, _P, _L, _P, _L, _I, _I, _I, _P, _P, _P, _L, _P, _P]),
-    "cn_head_bwd": (_I, [_I, _P, _L, _P, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P]),
-    "cn_upsample_sigmoid": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cn_upsample_sigmoid_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "cn_count_ge": (_I, [_P, _L, _F, _P, _P]),
-    "cn_loss_workspace_floats": (_S, [_L]),
-    "cn_bce_l1": (_I, [_P, _P, _L, _F, _F, _P, _P, _P, _P]),
-    "cn_bce_l1_devcount": (_I, [_P, _P, _L, _P, ctypes.c_double, _F, _P, _P, _P, _P]),
-    "cn_sgd": (_I, [_P, _I, _P, _F, _F, _P]),
-    "cn_rowdot": (_I, [_I, _P, _L, _P, _L, _I, _I, _P, _P]),
-    "cn_colsum": (_I, [_I, _P, _L, _I, _I, _P, _P, _P]),
-    "cn_cast2d": (_I, [_I, _I, _P, _L, _I, _I, _P, _L, _I, _P]),
-    "cn_build_source_hash": (ctypes.c_char_p, []),
-    "cn_build_experimental": (_I, []),
-    "cn_conv_wgrad_fp8_workspace_floats": (_S, [_I, _I, _I, _I, _I, _I, _I, _I]),
-    "cn_conv_wgrad_fp8": (_I, [_I, _P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I,
-                               _P, _P, _P, _P, _S, _P]),
-}
-
-_lib = None
+HEADER = os.path.join(_HERE, "..", "include", "cosnet_hip.h")
 
 
 class NativeError(RuntimeError):
     pass
+
+
+# The closed set of C types the ABI may use: by value these, any pointer as a void*, and a
+# const char* result.  A new type has to be admitted here on purpose: signatures() raises on
+# anything else instead of guessing int.
+_CTYPES = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+           "double": ctypes.c_double, "size_t": ctypes.c_size_t, "hipStream_t": ctypes.c_void_p}
+_RESTYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+
+
+def signatures(header_text):
+    """{name: (restype, [argtypes], [parameter names])} of every cn_* prototype in the text of
+    include/cosnet_hip.h: the header is the binding, nothing is transcribed by hand."""
+    text = re.sub(r"/\*.*?\*/", " ", header_text, flags=re.S)      # comments, also inside parameter lists
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    sigs = {}
+    for ret, name, params in re.findall(r"^(\w[\w \t*]*?)\s*\b(cn_\w+)\(([^)]*)\);", text, re.M):
+        if ret not in _RESTYPES:
+            raise NativeError("%s: result type %r is not one the binding admits" % (name, ret))
+        types, names = [], []
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            ctype, pname = re.fullmatch(r"(.*?)\s*(\w+)", " ".join(prm.split())).groups()
+            value = ctype[6:] if ctype.startswith("const ") else ctype
+            if "*" not in ctype and value not in _CTYPES:
+                raise NativeError("%s: parameter %r has type %r, not one the binding admits" % (name, pname, ctype))
+            types.append(ctypes.c_void_p if "*" in ctype else _CTYPES[value])
+            names.append(pname)
+        sigs[name] = (_RESTYPES[ret], types, names)
+    return sigs
+
+
+_sigs = None
+
+
+def _signatures():
+    global _sigs
+    if _sigs is None:
+        with open(HEADER) as fh:
+            _sigs = signatures(fh.read())
+    return _sigs
+
+
+_lib = None
 
 
 def load():
@@ -152,7 +75,7 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise NativeError("libcosnet_hip.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args, _) in _signatures().items():
         # an A/B build of an older tree (COSNET_HIP_LIB) may lack the newest entry points; the
         # in-tree product library must export every one
         if os.environ.get("COSNET_HIP_LIB") and not hasattr(lib, name):
@@ -191,7 +114,7 @@ def build_info():
 
 
 def exported_symbols():
-    return sorted(_SIGS.keys())
+    return sorted(_signatures())
 
 
 _ERR = {-1: "shape", -2: "alignment", -3: "unsupported", -4: "hip runtime"}
@@ -199,7 +122,11 @@ _ERR = {-1: "shape", -2: "alignment", -3: "unsupported", -4: "hip runtime"}
 
 def call(name, *args):
     """Invoke one C-ABI entry point; non-zero status -> NativeError."""
-    rc = getattr(load(), name)(*args)
+    try:
+        rc = getattr(load(), name)(*args)
+    except ctypes.ArgumentError as e:   # "argument 9: TypeError: ..." -> name the C parameter
+        i = int(re.match(r"argument (\d+)", str(e)).group(1))
+        raise NativeError("%s: argument %d (%s): %s" % (name, i, _signatures()[name][2][i - 1], e)) from e
     if rc != 0:
         raise NativeError("%s failed: %s (%d)" % (name, _ERR.get(rc, "hipError"), rc))
     return rc

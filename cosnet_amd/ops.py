@@ -4,6 +4,7 @@ Activations are 2-D tensors [P, C] = NHWC flattened, possibly a channel-slice vi
 wider buffer (row stride = t.stride(0)).  Every function launches HIP kernels from
 libcosnet_hip on the current torch stream; nothing here computes with torch ops.
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -40,6 +41,22 @@ def pool_out(h, k=3, s=2, p=1):
 def _ptrs(ts):
     """Host array of the data pointers of tensors `ts` (None: a null pointer)."""
     return (ctypes.c_void_p * len(ts))(*[nv.ptr(t) for t in ts])
+
+
+# ---- argument groups of the C ABI, each built in one place -----------------------------------
+def _mat(t, ld_none=None):
+    """(pointer, row stride) of a [P, C] matrix operand, for splatting into a call.  An optional
+    operand names ld_none, the stride that goes with its null pointer."""
+    return (None, ld_none) if t is None else (t.data_ptr(), ld(t))
+
+
+def _workspace(dev, size, *query_args, per=1, floor=0, dtype=torch.float32):
+    """(ws, n): launch scratch of n units -- n given, or asked of the *_workspace_* query that `size`
+    names -- as a tensor of n // per elements (per=4: a byte count held as floats), at least
+    `floor`; ws is None, a null pointer to the library, when that is nothing."""
+    n = size if isinstance(size, int) else int(nv.query(size, *query_args))
+    elems = max(n // per, floor)
+    return (torch.empty((elems,), dtype=dtype, device=dev) if elems else None), n
 
 
 # ---- train-mode BatchNorm bookkeeping shared by bn_stats and the conv + BN epilogues ----------
@@ -105,22 +122,38 @@ class GemmProfile:
         return out
 
 
-def _prof_start(flops, tag=None, nbytes=0):
+class _Launch:
+    """`with _profiled(...):` around a launch: the record's end event, recorded however the block
+    is left."""
+    __slots__ = ("e1",)
+
+    def __init__(self, e1):
+        self.e1 = e1
+
+    def __enter__(self):
+        pass
+
+    def __exit__(self, *a):
+        if self.e1 is not None:
+            self.e1.record()
+
+
+_UNPROFILED = _Launch(None)
+
+
+def _profiled(record, *args):
+    """Context of one GemmProfile record; record(*args) -> (flops, tag, nbytes) is worked out only
+    while a profile is active, so an unprofiled launch pays for none of it."""
     p = GemmProfile.active
-    if p is None:
-        return None
-    if torch.cuda.is_current_stream_capturing():
-        return None  # ROCm has no timing event nodes in graphs: profile an eager step instead
+    # ROCm has no timing event nodes in graphs: profile an eager step instead
+    if p is None or torch.cuda.is_current_stream_capturing():
+        return _UNPROFILED
+    flops, tag, nbytes = record(*args)
     e0 = torch.cuda.Event(enable_timing=True)
     e1 = torch.cuda.Event(enable_timing=True)
     e0.record()
     p.rec.append((flops, e0, e1, tag, nbytes))
-    return e1
-
-
-def _prof_end(e1):
-    if e1 is not None:
-        e1.record()
+    return _Launch(e1)
 
 
 # ---- weights -------------------------------------------------------------------------------
@@ -191,26 +224,63 @@ WCACHE = WeightCache()
 
 
 # ---- convolution ----------------------------------------------------------------------------
-def conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=None, out=None):
-    """x [n*h*w, >=cin] -> y [n*oh*ow, cout] (or written into `out`)."""
+# One conv problem, whichever of its three GEMMs runs: M output pixels, K = k*k*cin.
+_Conv = collections.namedtuple("_Conv", "n h w cin oh ow cout k M K")
+
+
+def _fwd_conv(x, n, h, w, wf, cout, k, stride, pad, dil, bias, out, out_dtype):
+    """What every forward conv wrapper starts from: (geometry, output -- allocated unless given --,
+    the operands its entry point starts with after the dtype, if it takes one)."""
     cin = wf.shape[1] // (k * k)
     oh, ow = out_hw(h, w, k, stride, pad, dil)
+    M = n * oh * ow
     if out is None:
-        out = torch.empty((n * oh * ow, cout), dtype=x.dtype, device=x.device)
-    es = x.element_size()
-    ev = _prof_start(2.0 * n * oh * ow * cout * k * k * cin, ("fwd", n * oh * ow, cout, k * k * cin),
-                     es * (n * h * w * cin + cout * k * k * cin + n * oh * ow * cout))
-    nws = fwd_split_floats(x, n * oh * ow, cout, k * k * cin)
-    if nws:   # deep one-round conv (the ASPP bottleneck): 256x256 tiles split over K
-        ws = torch.empty((nws,), dtype=torch.float32, device=x.device)
-        nv.call("cn_conv_fwd_ws", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, wf.data_ptr(), cout, k,
-                k, stride, pad, dil, nv.ptr(bias), out.data_ptr(), ld(out), oh, ow, ws.data_ptr(),
-                nws, nv.stream())
-    else:
-        nv.call("cn_conv_fwd", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, wf.data_ptr(), cout, k, k,
-                stride, pad, dil, nv.ptr(bias), out.data_ptr(), ld(out), oh, ow, nv.stream())
-    _prof_end(ev)
-    return out, oh, ow
+        out = torch.empty((M, cout), dtype=out_dtype, device=x.device)
+    return (_Conv(n, h, w, cin, oh, ow, cout, k, M, k * k * cin), out,
+            (x.data_ptr(), ld(x), n, h, w, cin, wf.data_ptr(), cout, k, k, stride, pad, dil, nv.ptr(bias),
+             out.data_ptr(), ld(out), oh, ow))
+
+
+def _fwd_record(tag, g, es_in, es_out, G=1):
+    """G forward convs of one input: x and the weights read, y written once."""
+    return (G * 2.0 * g.M * g.cout * g.K, (tag, g.M, g.cout * G, g.K),
+            es_in * (g.n * g.h * g.w * g.cin + G * g.cout * g.K) + es_out * G * g.M * g.cout)
+
+
+def _dgrad_conv(dy, n, oh, ow, wt, cin, k, spd, out, h, w, out_dtype):
+    """The same for the input-gradient wrappers; spd = (stride, pad, dil), or (pad, dil) for the
+    stride-1 entry points."""
+    cout = wt.shape[1] // (k * k)
+    if out is None:
+        out = torch.empty((n * h * w, cin), dtype=out_dtype, device=dy.device)
+    return (_Conv(n, h, w, cin, oh, ow, cout, k, n * oh * ow, k * k * cin), out,
+            (dy.data_ptr(), ld(dy), n, oh, ow, cout, wt.data_ptr(), cin, k, k, *spd, out.data_ptr(), ld(out),
+             h, w))
+
+
+def _dgrad_record(tag, g, es, es_x, over_input=False):
+    """dy and the weights read at es bytes, es_x bytes per element of x; over_input: the FLOPs
+    counted over the input pixels (the fp8 record), not the output pixels."""
+    P = g.n * g.h * g.w
+    return (2.0 * (P if over_input else g.M) * g.cout * g.K, (tag, P, g.cin, g.k * g.k * g.cout),
+            es * (g.M * g.cout + g.cout * g.K) + es_x * P * g.cin)
+
+
+def _wgrad_record(tag, G, es, n, h, w, cin, oh, ow, cout, k):
+    M, K = n * oh * ow, k * k * cin
+    return (G * 2.0 * M * cout * K, (tag, cout, K, M), G * (es * (n * h * w * cin + M * cout) + 4 * cout * K))
+
+
+def conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=None, out=None):
+    """x [n*h*w, >=cin] -> y [n*oh*ow, cout] (or written into `out`)."""
+    g, out, args = _fwd_conv(x, n, h, w, wf, cout, k, stride, pad, dil, bias, out, x.dtype)
+    with _profiled(_fwd_record, "fwd", g, x.element_size(), x.element_size()):
+        nws = fwd_split_floats(x, g.M, cout, g.K)
+        if nws:   # deep one-round conv (the ASPP bottleneck): 256x256 tiles split over K
+            nv.call("cn_conv_fwd_ws", dtc(x), *args, nv.ptr(_workspace(x.device, nws)[0]), nws, nv.stream())
+        else:
+            nv.call("cn_conv_fwd", dtc(x), *args, nv.stream())
+    return out, g.oh, g.ow
 
 
 def fwd_split_floats(x, m, cout, kdim):
@@ -218,33 +288,38 @@ def fwd_split_floats(x, m, cout, kdim):
     return int(nv.query("cn_conv_fwd_workspace_floats", dtc(x), m, cout, kdim))
 
 
+def _conv_fwd_bn_launch(name, head, dev, ws_dtype, g, bns, nseg, prof, arrays=False):
+    """Launches a conv + BN-statistics entry point: `head`, then the statistics tail all of them
+    share -- nseg, workspace, mean, invstd, running mean and variance (one set per BN of `bns`;
+    arrays=True: each as a host array of pointers), momentum, eps -- and counts the batches.
+    prof: the arguments of _fwd_record around g.  Returns [(mean, invstd)] per BN."""
+    nws = int(nv.query("cn_conv_fwd_bn_workspace_floats", ws_dtype, g.M, g.cout, g.K))
+    sets = []
+    for bn in bns:
+        mean = torch.empty((nseg * g.cout,), dtype=torch.float32, device=dev)
+        sets.append((_workspace(dev, nws)[0], mean, torch.empty_like(mean), bn.running_mean, bn.running_var))
+    tail = [_ptrs(col) if arrays else nv.ptr(col[0]) for col in zip(*sets)]
+    with _profiled(_fwd_record, prof[0], g, *prof[1:]):
+        nv.call(name, *head, nseg, *tail, _momentum(bns[0]), float(bns[0].eps), nv.stream())
+    for bn in bns:
+        _count_batches(bn, nseg)
+    return [(s[1], s[2]) for s in sets]
+
+
 def conv_fwd_bn(x, n, h, w, wf, cout, k, stride, pad, dil, bn, nseg=1, bias=None):
     """Train mode: y = conv(x) (+ bias) and the BN batch statistics of y from the GEMM epilogue
     (cn_conv_fwd_bn: no pass of its own over y).  Returns (y, oh, ow, (mean, invstd)) with
     [nseg*cout] statistics; bn.running_* updated once per segment like bn_stats."""
-    cin = wf.shape[1] // (k * k)
-    oh, ow = out_hw(h, w, k, stride, pad, dil)
-    M = n * oh * ow
-    _check_train_rows(M, nseg, cout)
-    if fwd_split_floats(x, M, cout, k * k * cin):
+    g, out, args = _fwd_conv(x, n, h, w, wf, cout, k, stride, pad, dil, bias, None, x.dtype)
+    _check_train_rows(g.M, nseg, cout)
+    if fwd_split_floats(x, g.M, cout, g.K):
         # split over K: the statistics come from their own pass over the reduced output
-        y, oh, ow = conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=bias)
-        return y, oh, ow, bn_stats(y, bn, True, nseg)
-    out = torch.empty((M, cout), dtype=x.dtype, device=x.device)
-    mean = torch.empty((nseg * cout,), dtype=torch.float32, device=x.device)
-    invstd = torch.empty_like(mean)
-    nws = int(nv.query("cn_conv_fwd_bn_workspace_floats", dtc(x), M, cout, k * k * cin))
-    ws = torch.empty((nws,), dtype=torch.float32, device=x.device)
+        conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=bias, out=out)
+        return out, g.oh, g.ow, bn_stats(out, bn, True, nseg)
     es = x.element_size()
-    ev = _prof_start(2.0 * M * cout * k * k * cin, ("fwd", M, cout, k * k * cin),
-                     es * (n * h * w * cin + cout * k * k * cin + M * cout))
-    nv.call("cn_conv_fwd_bn", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, wf.data_ptr(), cout, k, k,
-            stride, pad, dil, nv.ptr(bias), out.data_ptr(), ld(out), oh, ow, nseg, ws.data_ptr(),
-            mean.data_ptr(), invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-            _momentum(bn), float(bn.eps), nv.stream())
-    _prof_end(ev)
-    _count_batches(bn, nseg)
-    return out, oh, ow, (mean, invstd)
+    stats, = _conv_fwd_bn_launch("cn_conv_fwd_bn", (dtc(x), *args), x.device, dtc(x), g, [bn], nseg,
+                                 ("fwd", es, es))
+    return out, g.oh, g.ow, stats
 
 
 def conv_dgrad_bn(dy, n, oh, ow, wt, cin, k, pad, dil, x, stats, bn, dgamma=None, dbeta=None):
@@ -252,24 +327,18 @@ def conv_dgrad_bn(dy, n, oh, ow, wt, cin, k, pad, dil, x, stats, bn, dgamma=None
     pre-activation x [n*oh*ow, cin] fed the conv (cn_conv_dgrad_bn).  Returns
     (dy_bn [P, cin], dgamma, dbeta): the gradient at the BN output and the BN's parameter
     gradients (= the sums cn_bn_bwd_apply needs)."""
-    cout = wt.shape[1] // (k * k)
-    P = n * oh * ow
-    out = torch.empty((P, cin), dtype=dy.dtype, device=dy.device)
+    gm, out, args = _dgrad_conv(dy, n, oh, ow, wt, cin, k, (pad, dil), None, oh, ow, dy.dtype)
     if dgamma is None:
         dgamma = torch.empty((cin,), dtype=torch.float32, device=dy.device)
     if dbeta is None:
         dbeta = torch.empty((cin,), dtype=torch.float32, device=dy.device)
-    nws = int(nv.query("cn_conv_dgrad_bn_workspace_floats", dtc(dy), P, cin, k * k * cout))
-    ws = torch.empty((nws,), dtype=torch.float32, device=dy.device)
+    ws, _ = _workspace(dy.device, "cn_conv_dgrad_bn_workspace_floats", dtc(dy), gm.M, cin, k * k * gm.cout)
     es = dy.element_size()
-    ev = _prof_start(2.0 * P * cout * k * k * cin, ("dgrad1", P, cin, k * k * cout),
-                     es * (P * cout + cout * k * k * cin + 2 * P * cin))
     g, b = _affine(bn)
-    nv.call("cn_conv_dgrad_bn", dtc(dy), dy.data_ptr(), ld(dy), n, oh, ow, cout, wt.data_ptr(), cin,
-            k, k, pad, dil, out.data_ptr(), ld(out), oh, ow, x.data_ptr(), ld(x),
-            stats[0].data_ptr(), stats[1].data_ptr(), nv.ptr(g), nv.ptr(b), dbeta.data_ptr(),
-            dgamma.data_ptr(), ws.data_ptr(), nv.stream())
-    _prof_end(ev)
+    with _profiled(_dgrad_record, "dgrad1", gm, es, 2 * es):
+        # the C names of the two sums are sum_dz (= dbeta) and sum_dzxh (= dgamma), in this order
+        nv.call("cn_conv_dgrad_bn", dtc(dy), *args, *_mat(x), stats[0].data_ptr(), stats[1].data_ptr(),
+                nv.ptr(g), nv.ptr(b), dbeta.data_ptr(), dgamma.data_ptr(), nv.ptr(ws), nv.stream())
     return out, dgamma, dbeta
 
 
@@ -279,9 +348,9 @@ def bn_bwd_apply(x, dy, stats, bn, dgamma, dbeta, out=None):
     if out is None:
         out = torch.empty((p, c), dtype=x.dtype, device=x.device)
     g, b = _affine(bn)
-    nv.call("cn_bn_bwd_apply", dtc(x), x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), p, c,
-            stats[0].data_ptr(), stats[1].data_ptr(), nv.ptr(g), nv.ptr(b), dbeta.data_ptr(),
-            dgamma.data_ptr(), out.data_ptr(), ld(out), nv.stream())
+    nv.call("cn_bn_bwd_apply", dtc(x), *_mat(x), *_mat(dy), p, c, stats[0].data_ptr(),
+            stats[1].data_ptr(), nv.ptr(g), nv.ptr(b), dbeta.data_ptr(), dgamma.data_ptr(), *_mat(out),
+            nv.stream())
     return out
 
 
@@ -304,8 +373,8 @@ def fp8_quant(x, state, mode=FP8_CURRENT, out=None, fmt=FP8_E4M3):
     p, c = x.shape
     if out is None and mode != FP8_AMAX:
         out = torch.empty((p, c), dtype=torch.uint8, device=x.device)
-    nv.call("cn_fp8_quant_fmt", dtc(x), fmt, x.data_ptr(), ld(x), p, c, nv.ptr(out),
-            ld(out) if out is not None else c, state.data_ptr(), mode, nv.stream())
+    nv.call("cn_fp8_quant_fmt", dtc(x), fmt, *_mat(x), p, c, *_mat(out, c), state.data_ptr(), mode,
+            nv.stream())
     return out
 
 
@@ -319,47 +388,32 @@ def fp8_quant_static(x, state, out=None, fmt=FP8_E4M3):
     p, c = x.shape
     if out is None:
         out = torch.empty((p, c), dtype=torch.uint8, device=x.device)
-    nv.call("cn_fp8_quant_static", dtc(x), fmt, x.data_ptr(), ld(x), p, c, out.data_ptr(), ld(out),
-            state.data_ptr(), nv.stream())
+    nv.call("cn_fp8_quant_static", dtc(x), fmt, *_mat(x), p, c, *_mat(out), state.data_ptr(), nv.stream())
     return out
 
 
 def bcast_rows_u8(src, n, hw, out):
     """out[(i*hw + p), :] = src[i, :] over bytes (src [n, C] contiguous, out a [n*hw, C] view)."""
-    nv.call("cn_bcast_rows_u8", src.data_ptr(), n, hw, src.shape[1], out.data_ptr(), ld(out),
-            nv.stream())
+    nv.call("cn_bcast_rows_u8", src.data_ptr(), n, hw, src.shape[1], *_mat(out), nv.stream())
     return out
 
 
 def conv_dgrad_fp8(dy8, n, oh, ow, wt8, cin, k, pad, dil, h, w, dy_state, w_state, out=None,
                    accumulate=False):
     """dx (bf16) (+)= conv_dgrad(dy8 e5m2, wt8 e4m3) * s_dy * s_w, stride 1 (fp8 mode)."""
-    cout = wt8.shape[1] // (k * k)
-    if out is None:
-        out = torch.empty((n * h * w, cin), dtype=torch.bfloat16, device=dy8.device)
-    ev = _prof_start(2.0 * n * h * w * cin * k * k * cout, ("dgrad8", n * h * w, cin, k * k * cout),
-                     n * oh * ow * cout + cin * k * k * cout + 2 * n * h * w * cin)
-    nv.call("cn_conv_dgrad_fp8", dy8.data_ptr(), ld(dy8), n, oh, ow, cout, wt8.data_ptr(), cin, k, k,
-            pad, dil, out.data_ptr(), ld(out), h, w, int(accumulate), dy_state.data_ptr(),
-            w_state.data_ptr(), nv.stream())
-    _prof_end(ev)
+    g, out, args = _dgrad_conv(dy8, n, oh, ow, wt8, cin, k, (pad, dil), out, h, w, torch.bfloat16)
+    with _profiled(_dgrad_record, "dgrad8", g, 1, 2, True):   # one-byte operands, a two-byte output
+        nv.call("cn_conv_dgrad_fp8", *args, int(accumulate), dy_state.data_ptr(), w_state.data_ptr(), nv.stream())
     return out
 
 
 def conv_fwd_fp8(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_state, bias=None,
                  out=None):
     """y (bf16) = conv(x8, w8) * sx * sw (+ bias): the fp8 implicit-GEMM conv."""
-    cin = wf8.shape[1] // (k * k)
-    oh, ow = out_hw(h, w, k, stride, pad, dil)
-    if out is None:
-        out = torch.empty((n * oh * ow, cout), dtype=torch.bfloat16, device=x8.device)
-    ev = _prof_start(2.0 * n * oh * ow * cout * k * k * cin, ("fwd8", n * oh * ow, cout, k * k * cin),
-                     n * h * w * cin + cout * k * k * cin + 2 * n * oh * ow * cout)
-    nv.call("cn_conv_fwd_fp8", x8.data_ptr(), ld(x8), n, h, w, cin, wf8.data_ptr(), cout, k, k,
-            stride, pad, dil, nv.ptr(bias), out.data_ptr(), ld(out), oh, ow, x_state.data_ptr(),
-            w_state.data_ptr(), nv.stream())
-    _prof_end(ev)
-    return out, oh, ow
+    g, out, args = _fwd_conv(x8, n, h, w, wf8, cout, k, stride, pad, dil, bias, out, torch.bfloat16)
+    with _profiled(_fwd_record, "fwd8", g, 1, 2):
+        nv.call("cn_conv_fwd_fp8", *args, x_state.data_ptr(), w_state.data_ptr(), nv.stream())
+    return out, g.oh, g.ow
 
 
 def conv_fwd_bn_grouped(x, n, h, w, wfs, cout, k, dils, bns, nseg=1, biases=None):
@@ -368,63 +422,34 @@ def conv_fwd_bn_grouped(x, n, h, w, wfs, cout, k, dils, bns, nseg=1, biases=None
     statistics of y_g from the GEMM epilogue (as conv_fwd_bn).  Returns [(y_g, (mean, invstd))]."""
     G = len(wfs)
     cin = wfs[0].shape[1] // (k * k)
-    M = n * h * w
-    _check_train_rows(M, nseg, cout)
-    dev = x.device
-    ys = [torch.empty((M, cout), dtype=x.dtype, device=dev) for _ in range(G)]
-    means = [torch.empty((nseg * cout,), dtype=torch.float32, device=dev) for _ in range(G)]
-    invs = [torch.empty_like(m) for m in means]
-    nws = int(nv.query("cn_conv_fwd_bn_workspace_floats", dtc(x), M, cout, k * k * cin))
-    wss = [torch.empty((nws,), dtype=torch.float32, device=dev) for _ in range(G)]
-    biases = biases or [None] * G
+    g = _Conv(n, h, w, cin, h, w, cout, k, n * h * w, k * k * cin)   # 'same' convs: oh, ow = h, w
+    _check_train_rows(g.M, nseg, cout)
+    ys = [torch.empty((g.M, cout), dtype=x.dtype, device=x.device) for _ in range(G)]
     es = x.element_size()
-    ev = _prof_start(2.0 * G * M * cout * k * k * cin, ("fwd", M, cout * G, k * k * cin),
-                     es * (n * h * w * cin + G * cout * k * k * cin + G * M * cout))
-    nv.call("cn_conv_fwd_bn_grouped", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, G, _ptrs(wfs), cout,
-            k, k, (ctypes.c_int * G)(*dils), _ptrs(biases), _ptrs(ys), cout, nseg, _ptrs(wss),
-            _ptrs(means), _ptrs(invs), _ptrs([b.running_mean for b in bns]),
-            _ptrs([b.running_var for b in bns]), _momentum(bns[0]), float(bns[0].eps), nv.stream())
-    _prof_end(ev)
-    for b in bns:
-        _count_batches(b, nseg)
-    return [(y, (m, i)) for y, m, i in zip(ys, means, invs)]
+    stats = _conv_fwd_bn_launch(
+        "cn_conv_fwd_bn_grouped",
+        (dtc(x), *_mat(x), n, h, w, g.cin, G, _ptrs(wfs), cout, k, k, (ctypes.c_int * G)(*dils),
+         _ptrs(biases or [None] * G), _ptrs(ys), cout),
+        x.device, dtc(x), g, bns, nseg, ("fwd", es, es, G), arrays=True)
+    return list(zip(ys, stats))
 
 
 def conv_fwd_fp8_bn(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_state, bn, nseg=1,
                     bias=None):
     """conv_fwd_fp8 + the BN batch statistics of its stored bf16 output from the GEMM epilogue
     (cn_conv_fwd_fp8_bn), as conv_fwd_bn does for bf16.  Returns (y, oh, ow, (mean, invstd))."""
-    cin = wf8.shape[1] // (k * k)
-    oh, ow = out_hw(h, w, k, stride, pad, dil)
-    M = n * oh * ow
-    _check_train_rows(M, nseg, cout)
-    out = torch.empty((M, cout), dtype=torch.bfloat16, device=x8.device)
-    mean = torch.empty((nseg * cout,), dtype=torch.float32, device=x8.device)
-    invstd = torch.empty_like(mean)
-    nws = int(nv.query("cn_conv_fwd_bn_workspace_floats", 2, M, cout, k * k * cin))
-    ws = torch.empty((nws,), dtype=torch.float32, device=x8.device)
-    ev = _prof_start(2.0 * M * cout * k * k * cin, ("fwd8", M, cout, k * k * cin),
-                     n * h * w * cin + cout * k * k * cin + 2 * M * cout)
-    nv.call("cn_conv_fwd_fp8_bn", x8.data_ptr(), ld(x8), n, h, w, cin, wf8.data_ptr(), cout, k, k,
-            stride, pad, dil, nv.ptr(bias), out.data_ptr(), ld(out), oh, ow, x_state.data_ptr(),
-            w_state.data_ptr(), nseg, ws.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), _momentum(bn), float(bn.eps),
-            nv.stream())
-    _prof_end(ev)
-    _count_batches(bn, nseg)
-    return out, oh, ow, (mean, invstd)
+    g, out, args = _fwd_conv(x8, n, h, w, wf8, cout, k, stride, pad, dil, bias, None, torch.bfloat16)
+    _check_train_rows(g.M, nseg, cout)
+    stats, = _conv_fwd_bn_launch("cn_conv_fwd_fp8_bn", (*args, x_state.data_ptr(), w_state.data_ptr()),
+                                 x8.device, 2, g, [bn], nseg, ("fwd8", 1, 2))   # workspace query: dtype 2 = fp8
+    return out, g.oh, g.ow, stats
 
 
 def conv_dgrad(dy, n, oh, ow, wt, cin, k, stride, pad, dil, h, w, out=None, accumulate=False):
-    cout = wt.shape[1] // (k * k)
-    if out is None:
-        out = torch.empty((n * h * w, cin), dtype=dy.dtype, device=dy.device)
+    g, out, args = _dgrad_conv(dy, n, oh, ow, wt, cin, k, (stride, pad, dil), out, h, w, dy.dtype)
     es = dy.element_size()
-    ev = _prof_start(2.0 * n * oh * ow * cout * k * k * cin, ("dgrad%d" % stride, n * h * w, cin, k * k * cout),
-                     es * (n * oh * ow * cout + cout * k * k * cin + n * h * w * cin))
-    nv.call("cn_conv_dgrad", dtc(dy), dy.data_ptr(), ld(dy), n, oh, ow, cout, wt.data_ptr(), cin,
-            k, k, stride, pad, dil, out.data_ptr(), ld(out), h, w, int(accumulate), nv.stream())
-    _prof_end(ev)
+    with _profiled(_dgrad_record, "dgrad%d" % stride, g, es, es):
+        nv.call("cn_conv_dgrad", dtc(dy), *args, int(accumulate), nv.stream())
     return out
 
 
@@ -432,14 +457,10 @@ def conv_wgrad(x, n, h, w, cin, dy, oh, ow, cout, k, stride, pad, dil, dw=None):
     """fp32 [cout, k*k*cin] weight gradient (channels_last order), fully overwritten."""
     if dw is None:
         dw = torch.empty((cout, k * k * cin), dtype=torch.float32, device=x.device)
-    nws = int(nv.query("cn_conv_wgrad_workspace_floats", dtc(x), n, oh, ow, cout, k, k, cin))
-    ws = torch.empty((nws,), dtype=torch.float32, device=x.device) if nws else None
-    es = x.element_size()
-    ev = _prof_start(2.0 * n * oh * ow * cout * k * k * cin, ("wgrad", cout, k * k * cin, n * oh * ow),
-                     es * (n * h * w * cin + n * oh * ow * cout) + 4 * cout * k * k * cin)
-    nv.call("cn_conv_wgrad", dtc(x), x.data_ptr(), ld(x), n, h, w, cin, dy.data_ptr(), ld(dy), oh,
-            ow, cout, k, k, stride, pad, dil, dw.data_ptr(), nv.ptr(ws), nv.stream())
-    _prof_end(ev)
+    ws, _ = _workspace(x.device, "cn_conv_wgrad_workspace_floats", dtc(x), n, oh, ow, cout, k, k, cin)
+    with _profiled(_wgrad_record, "wgrad", 1, x.element_size(), n, h, w, cin, oh, ow, cout, k):
+        nv.call("cn_conv_wgrad", dtc(x), *_mat(x), n, h, w, cin, *_mat(dy), oh, ow, cout, k, k, stride, pad,
+                dil, dw.data_ptr(), nv.ptr(ws), nv.stream())
     return dw
 
 
@@ -465,22 +486,16 @@ def conv_wgrad_grouped(jobs, n, h, w, cin, oh, ow, cout, k, stride, pad, dil, sp
     [cout, k*k*cin] (written).  No split-K workspace and no reduce launch.  split=True: the G
     problems also split over K (cn_conv_wgrad_grouped_ws: one GEMM launch + one reduce launch
     for the group), for shapes too small to fill the chip grouped whole."""
-    g, x0, dy0 = _group_of(jobs, 0, 1)
+    G, x0, dy0 = _group_of(jobs, 0, 1)
     xs, dys, dws = (_ptrs(ts) for ts in zip(*jobs))
-    es = x0.element_size()
-    fl = 2.0 * n * oh * ow * cout * k * k * cin
-    ev = _prof_start(g * fl, ("wgrad", cout, k * k * cin, n * oh * ow),
-                     g * (es * (n * h * w * cin + n * oh * ow * cout) + 4 * cout * k * k * cin))
-    nws = int(nv.query("cn_conv_wgrad_grouped_workspace_floats", dtc(x0), g, n, oh, ow, cout, k, k,
-                       cin)) if split else 0
-    if nws:
-        ws = torch.empty((nws,), dtype=torch.float32, device=x0.device)
-        nv.call("cn_conv_wgrad_grouped_ws", dtc(x0), g, xs, ld(x0), n, h, w, cin, dys, ld(dy0), oh, ow,
-                cout, k, k, stride, pad, dil, dws, ws.data_ptr(), nws, nv.stream())
-    else:
-        nv.call("cn_conv_wgrad_grouped", dtc(x0), g, xs, ld(x0), n, h, w, cin, dys, ld(dy0), oh, ow,
-                cout, k, k, stride, pad, dil, dws, nv.stream())
-    _prof_end(ev)
+    args = (dtc(x0), G, xs, ld(x0), n, h, w, cin, dys, ld(dy0), oh, ow, cout, k, k, stride, pad, dil, dws)
+    with _profiled(_wgrad_record, "wgrad", G, x0.element_size(), n, h, w, cin, oh, ow, cout, k):
+        ws, nws = _workspace(x0.device, "cn_conv_wgrad_grouped_workspace_floats", dtc(x0), G, n, oh, ow, cout,
+                             k, k, cin) if split else (None, 0)
+        if nws:
+            nv.call("cn_conv_wgrad_grouped_ws", *args, nv.ptr(ws), nws, nv.stream())
+        else:
+            nv.call("cn_conv_wgrad_grouped", *args, nv.stream())
     return [dw for _, _, dw in jobs]
 
 
@@ -490,16 +505,12 @@ def conv_wgrad_fp8(jobs, n, h, w, cin, oh, ow, cout, k, stride, pad, dil):
     fp8 forward conv's input copy), dy8 e5m2 [n*oh*ow, cout] (the fp8 dgrad's output-gradient
     copy), their [4]-float scale states (element 0 = dequantisation scale) and dw fp32
     [cout, k*k*cin] (written).  Split over K into slabs + one reduce launch when small."""
-    g, x0, d0 = _group_of(jobs, 0, 2)
+    G, x0, d0 = _group_of(jobs, 0, 2)
     xs, xst, dys, dst, dws = (_ptrs(ts) for ts in zip(*jobs))
-    fl = 2.0 * n * oh * ow * cout * k * k * cin
-    ev = _prof_start(g * fl, ("wgrad8", cout, k * k * cin, n * oh * ow),
-                     g * ((n * h * w * cin + n * oh * ow * cout) + 4 * cout * k * k * cin))
-    nws = int(nv.query("cn_conv_wgrad_fp8_workspace_floats", g, n, oh, ow, cout, k, k, cin))
-    ws = torch.empty((nws,), dtype=torch.float32, device=x0.device) if nws else None
-    nv.call("cn_conv_wgrad_fp8", g, xs, ld(x0), n, h, w, cin, dys, ld(d0), oh, ow, cout, k, k, stride,
-            pad, dil, dws, xst, dst, nv.ptr(ws), nws, nv.stream())
-    _prof_end(ev)
+    with _profiled(_wgrad_record, "wgrad8", G, 1, n, h, w, cin, oh, ow, cout, k):
+        ws, nws = _workspace(x0.device, "cn_conv_wgrad_fp8_workspace_floats", G, n, oh, ow, cout, k, k, cin)
+        nv.call("cn_conv_wgrad_fp8", G, xs, ld(x0), n, h, w, cin, dys, ld(d0), oh, ow, cout, k, k, stride,
+                pad, dil, dws, xst, dst, nv.ptr(ws), nws, nv.stream())
     return [j[4] for j in jobs]
 
 
@@ -513,8 +524,7 @@ def as_param_grad(dw_flat, weight):
 
 def colpart_ws(p, c, device):
     """Workspace of the deterministic column reductions (colsum, gate / head backward)."""
-    n = int(nv.query("cn_colpart_workspace_floats", p, c))
-    return torch.empty((max(n, 1),), dtype=torch.float32, device=device)
+    return _workspace(device, "cn_colpart_workspace_floats", p, c, floor=1)[0]
 
 
 def colsum(x, out=None):
@@ -522,8 +532,8 @@ def colsum(x, out=None):
     if out is None:
         out = torch.empty((x.shape[1],), dtype=torch.float32, device=x.device)
     ws = colpart_ws(x.shape[0], x.shape[1], x.device)
-    nv.call("cn_colsum", dtc(x), x.data_ptr(), ld(x), x.shape[0], x.shape[1], out.data_ptr(),
-            ws.data_ptr(), nv.stream())
+    nv.call("cn_colsum", dtc(x), *_mat(x), x.shape[0], x.shape[1], out.data_ptr(), ws.data_ptr(),
+            nv.stream())
     return out
 
 
@@ -532,10 +542,9 @@ def avgpool(x, n, hw, scale, out):
     deterministic fixed-order reduction of row-split partials (AdaptiveAvgPool2d(1),
     deeplab/deeplabv3_encoder.py:57; and its backward with scale 1)."""
     c = out.shape[1]
-    nws = int(nv.query("cn_avgpool_workspace_floats", dtc(x), n, hw, c))
-    ws = torch.empty((max(nws, 1),), dtype=torch.float32, device=x.device)
-    nv.call("cn_avgpool", dtc(x), x.data_ptr(), ld(x), n, hw, c, float(scale), out.data_ptr(),
-            ws.data_ptr(), nv.stream())
+    ws, _ = _workspace(x.device, "cn_avgpool_workspace_floats", dtc(x), n, hw, c, floor=1)
+    nv.call("cn_avgpool", dtc(x), *_mat(x), n, hw, c, float(scale), out.data_ptr(), ws.data_ptr(),
+            nv.stream())
     return out
 
 
@@ -552,27 +561,24 @@ def gemm(a, b, m, n, k, layout_a=GEMM_KC, layout_b=GEMM_KC, lda=None, ldb=None, 
         ldc = n
         c_bs = m * n
     c_f32 = int(out.dtype == torch.float32)
-    ev = _prof_start(2.0 * batch * m * n * (kb_lim if kb_lim is not None else k),
-                     (tag or "gemm%d%d" % (layout_a, layout_b), batch * m, n, k),
-                     (batch if a_bs else 1) * m * k * a.element_size() +
-                     (batch if b_bs else 1) * n * k * b.element_size() +
-                     batch * m * n * out.element_size())
-    if nsplit > 1 and c_mode in (0, 1) and batch == 1 and c_f32 and ldc == n:
-        # split-K into fp32 slabs + fixed-order reduction (no atomic contention)
-        slab = m * n
-        ws = torch.empty((nsplit * slab,), dtype=torch.float32, device=a.device)
-        nv.call("cn_gemm", nv.dtype_code(dt), layout_a, layout_b, m, n, k,
-                k if ka_lim is None else ka_lim, k if kb_lim is None else kb_lim,
-                a.data_ptr(), lda, a_bs, b.data_ptr(), ldb, b_bs, ws.data_ptr(), ldc, 0, 1,
-                3, float(alpha), None, 1, nsplit, slab, nv.stream())
-        nv.call("cn_splitk_reduce", ws.data_ptr(), _nsplit_eff(k, nsplit, dt), slab, slab,
-                out.data_ptr(), int(c_mode == 1), nv.stream())
-    else:
-        nv.call("cn_gemm", nv.dtype_code(dt), layout_a, layout_b, m, n, k,
-                k if ka_lim is None else ka_lim, k if kb_lim is None else kb_lim,
-                a.data_ptr(), lda, a_bs, b.data_ptr(), ldb, b_bs, out.data_ptr(), ldc, c_bs, c_f32,
-                c_mode, float(alpha), nv.ptr(bias), batch, nsplit, 0, nv.stream())
-    _prof_end(ev)
+    ab = (nv.dtype_code(dt), layout_a, layout_b, m, n, k, k if ka_lim is None else ka_lim,
+          k if kb_lim is None else kb_lim, a.data_ptr(), lda, a_bs, b.data_ptr(), ldb, b_bs)
+    with _profiled(lambda: (2.0 * batch * m * n * (kb_lim if kb_lim is not None else k),
+                            (tag or "gemm%d%d" % (layout_a, layout_b), batch * m, n, k),
+                            (batch if a_bs else 1) * m * k * a.element_size() +
+                            (batch if b_bs else 1) * n * k * b.element_size() +
+                            batch * m * n * out.element_size())):
+        if nsplit > 1 and c_mode in (0, 1) and batch == 1 and c_f32 and ldc == n:
+            # split-K into fp32 slabs + fixed-order reduction (no atomic contention)
+            slab = m * n
+            ws = torch.empty((nsplit * slab,), dtype=torch.float32, device=a.device)
+            nv.call("cn_gemm", *ab, ws.data_ptr(), ldc, 0, 1, 3, float(alpha), None, 1, nsplit, slab,
+                    nv.stream())
+            nv.call("cn_splitk_reduce", ws.data_ptr(), _nsplit_eff(k, nsplit, dt), slab, slab,
+                    out.data_ptr(), int(c_mode == 1), nv.stream())
+        else:
+            nv.call("cn_gemm", *ab, out.data_ptr(), ldc, c_bs, c_f32, c_mode, float(alpha), nv.ptr(bias),
+                    batch, nsplit, 0, nv.stream())
     return out
 
 
@@ -587,19 +593,29 @@ def coatt_fused_ok(dt, c, va, vb):
             and ld(vb) % 8 == 0 and va.data_ptr() % 16 == 0 and vb.data_ptr() % 16 == 0)
 
 
+def _coatt_args(vat, va, vb, n, hw, za, zb, idx=()):
+    """The operand group every co-attention forward starts with: the three feature matrices, (the
+    frame maps of the indexed form,) the pair geometry and the outputs, whose row stride comes
+    from za if present, otherwise from zb."""
+    return (*_mat(vat), *_mat(va), *_mat(vb), *idx, n, hw, vat.shape[1], nv.ptr(za), nv.ptr(zb),
+            ld(za if za is not None else zb))
+
+
+def _coatt_record(tag, vat, n, hw, nprod, nmat):
+    """A co-attention launch over n pairs: nprod x HW^2 C FLOPs per pair and nmat [n*hw, C] matrices
+    read or written once."""
+    c = vat.shape[1]
+    return nprod * n * hw * hw * c, (tag, n, hw, c), nmat * n * hw * c * vat.element_size()
+
+
 def coatt_fused(vat, va, vb, n, hw, za=None, zb=None):
     """Z_a = softmax_j(S) Vb and Z_b = softmax_i(S)^T Va with S = vat vb^T, never materialised
     (rgbd_segmentation_RAA.py:160-170).  Algorithmic work: 3 x 2 HW^2 C per pair."""
-    c = vat.shape[1]
-    ev = _prof_start(3 * 2.0 * n * hw * hw * c, ("coatt_fused", n, hw, c),
-                     (3 * n * hw * c + 2 * n * hw * c) * vat.element_size())
     ndir = (za is not None) + (zb is not None)
-    nws = int(nv.query("cn_coatt_fused_workspace_bytes", n, hw, ndir))
-    ws = torch.empty((nws // 4,), dtype=torch.float32, device=vat.device) if nws else None
-    nv.call("cn_coatt_fused_fwd_ws", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), vb.data_ptr(),
-            ld(vb), n, hw, c, nv.ptr(za), nv.ptr(zb), ld(za if za is not None else zb), nv.ptr(ws),
-            nws, nv.stream())
-    _prof_end(ev)
+    with _profiled(_coatt_record, "coatt_fused", vat, n, hw, 3 * 2.0, 5):   # both directions counted, whatever ndir
+        ws, nws = _workspace(vat.device, "cn_coatt_fused_workspace_bytes", n, hw, ndir, per=4)
+        nv.call("cn_coatt_fused_fwd_ws", *_coatt_args(vat, va, vb, n, hw, za, zb), nv.ptr(ws), nws,
+                nv.stream())
     return za, zb
 
 
@@ -616,16 +632,12 @@ def coatt_fused_idx(vat, va, vb, ia, ib, p, hw, za=None, zb=None):
     va) with b-role frame ib[i] (rows of vb); ia / ib int32[p] on the GPU (None: frame i).  Outputs
     stacked [p*hw, C]; either may be None (rgbd_segmentation_RAA.py:160-170 per pair of
     test.py:287-305, every frame stored once)."""
-    c = vat.shape[1]
     ndir = (za is not None) + (zb is not None)
-    ev = _prof_start(3 * ndir * 1.0 * p * hw * hw * c, ("coatt_fused_idx", p, hw, c),
-                     (3 * p * hw * c + ndir * p * hw * c) * vat.element_size())
-    nws = int(nv.query("cn_coatt_fused_workspace_bytes", p, hw, ndir))
-    ws = torch.empty((nws // 4,), dtype=torch.float32, device=vat.device) if nws else None
-    nv.call("cn_coatt_fused_fwd_idx", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), vb.data_ptr(),
-            ld(vb), _idx(ia, p), _idx(ib, p), p, hw, c, nv.ptr(za), nv.ptr(zb),
-            ld(za if za is not None else zb), nv.ptr(ws), nws, nv.stream())
-    _prof_end(ev)
+    with _profiled(_coatt_record, "coatt_fused_idx", vat, p, hw, 3 * ndir * 1.0, 3 + ndir):
+        ws, nws = _workspace(vat.device, "cn_coatt_fused_workspace_bytes", p, hw, ndir, per=4)
+        nv.call("cn_coatt_fused_fwd_idx",
+                *_coatt_args(vat, va, vb, p, hw, za, zb, idx=(_idx(ia, p), _idx(ib, p))), nv.ptr(ws), nws,
+                nv.stream())
     return za, zb
 
 
@@ -635,8 +647,8 @@ def gate_cat_idx(z, vbank, iv, p, hw, g, gb=None, out=None):
     c = z.shape[1]
     if out is None:
         out = torch.empty((p * hw, 2 * c), dtype=z.dtype, device=z.device)
-    nv.call("cn_gate_cat_idx", dtc(z), z.data_ptr(), ld(z), vbank.data_ptr(), ld(vbank), _idx(iv, p),
-            p, hw, c, g.reshape(-1).data_ptr(), nv.ptr(gb), out.data_ptr(), ld(out), nv.stream())
+    nv.call("cn_gate_cat_idx", dtc(z), *_mat(z), *_mat(vbank), _idx(iv, p), p, hw, c,
+            g.reshape(-1).data_ptr(), nv.ptr(gb), *_mat(out), nv.stream())
     return out
 
 
@@ -660,15 +672,10 @@ def coatt_f8(vat, va, vb, n, hw, za, zb, lse_a=None, lse_b=None):
     """Both co-attention directions with MX-fp8 operands (BASELINE configs[4]: e4m3 bytes + one
     E8M0 exponent per 32 reduction values, the block-scaled 32x32x64 MFMA), softmax statistics
     in fp32; optional per-row log2-sum-exp2 [n, hw_pad(hw)] for the bf16 flash backward."""
-    c = vat.shape[1]
-    ev = _prof_start(3 * 2.0 * n * hw * hw * c, ("coatt_f8_fwd", n, hw, c),
-                     (3 * n * hw * c + 2 * n * hw * c) * vat.element_size())
-    nws = int(nv.query("cn_coatt_f8_workspace_bytes", n, hw))
-    ws = torch.empty((nws,), dtype=torch.uint8, device=vat.device)
-    nv.call("cn_coatt_f8_fwd", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), vb.data_ptr(), ld(vb),
-            n, hw, c, za.data_ptr(), zb.data_ptr(), ld(za), nv.ptr(lse_a), nv.ptr(lse_b),
-            ws.data_ptr(), nws, nv.stream())
-    _prof_end(ev)
+    with _profiled(_coatt_record, "coatt_f8_fwd", vat, n, hw, 3 * 2.0, 5):
+        ws, nws = _workspace(vat.device, "cn_coatt_f8_workspace_bytes", n, hw, dtype=torch.uint8)
+        nv.call("cn_coatt_f8_fwd", *_coatt_args(vat, va, vb, n, hw, za, zb), nv.ptr(lse_a),
+                nv.ptr(lse_b), nv.ptr(ws), nws, nv.stream())
     return za, zb
 
 
@@ -683,10 +690,8 @@ def coatt_f8_bank(vat, va, t, hw):
             raise ValueError("coatt_f8_bank: vat / va must be bf16 [>= %d, C] tensors on the GPU" % (t * hw))
     nb = int(nv.query("cn_coatt_f8_bank_bytes", t, hw))
     img = torch.empty((nb,), dtype=torch.uint8, device=vat.device)
-    ev = _prof_start(0.0, ("coatt_f8_bank_build", t, hw, c), 2 * t * hw * c * vat.element_size() + nb)
-    nv.call("cn_coatt_f8_bank_build", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), t, hw, c,
-            img.data_ptr(), nb, nv.stream())
-    _prof_end(ev)
+    with _profiled(lambda: (0.0, ("coatt_f8_bank_build", t, hw, c), 2 * t * hw * c * vat.element_size() + nb)):
+        nv.call("cn_coatt_f8_bank_build", *_mat(vat), *_mat(va), t, hw, c, img.data_ptr(), nb, nv.stream())
     return img
 
 
@@ -706,11 +711,10 @@ def coatt_f8_idx(img, img2, t, ia, ib, p, hw, za, za2=None):
         if im.dtype != torch.uint8 or not im.is_cuda or not im.is_contiguous() or im.numel() < nb:
             raise ValueError("coatt_f8_idx: an image bank of coatt_f8_bank(., ., %d, %d) is expected" % (t, hw))
     # a side only: 2 products of 2 P HW^2 C per modality; operands are one byte per value
-    ev = _prof_start(nmod * 2 * 2.0 * p * hw * hw * c, ("coatt_f8_fwd_idx", p, hw, c),
-                     nmod * (3 * p * hw * c + p * hw * c * za.element_size()))
-    nv.call("cn_coatt_f8_fwd_idx", img.data_ptr(), nv.ptr(img2), t, _idx(ia, p), _idx(ib, p), p, hw, c,
-            za.data_ptr(), nv.ptr(za2), ld(za), nv.stream())
-    _prof_end(ev)
+    with _profiled(lambda: (nmod * 2 * 2.0 * p * hw * hw * c, ("coatt_f8_fwd_idx", p, hw, c),
+                            nmod * (3 * p * hw * c + p * hw * c * za.element_size()))):
+        nv.call("cn_coatt_f8_fwd_idx", img.data_ptr(), nv.ptr(img2), t, _idx(ia, p), _idx(ib, p), p, hw,
+                c, za.data_ptr(), nv.ptr(za2), ld(za), nv.stream())
     return za, za2
 
 
@@ -719,30 +723,22 @@ def coatt_f8_train(vat, va, vb, n, hw, za, zb, lse_a, lse_b):
     per-row log2-sum-exp2 normalisers, and the decoded operands (vat_q, va_q, vb_q) -- bf16,
     exact -- that the flash backward recomputes S and P from (cn_coatt_f8_train_fwd)."""
     c = vat.shape[1]
-    ev = _prof_start(3 * 2.0 * n * hw * hw * c, ("coatt_f8_train_fwd", n, hw, c),
-                     (3 * n * hw * c + 2 * n * hw * c) * vat.element_size())
-    nws = int(nv.query("cn_coatt_f8_train_workspace_bytes", n, hw))
-    ws = torch.empty((nws,), dtype=torch.uint8, device=vat.device)
     q = [torch.empty((n * hw, c), dtype=torch.bfloat16, device=vat.device) for _ in range(3)]
-    nv.call("cn_coatt_f8_train_fwd", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), vb.data_ptr(),
-            ld(vb), n, hw, c, za.data_ptr(), zb.data_ptr(), ld(za), lse_a.data_ptr(), lse_b.data_ptr(),
-            q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), c, ws.data_ptr(), nws, nv.stream())
-    _prof_end(ev)
+    with _profiled(_coatt_record, "coatt_f8_train_fwd", vat, n, hw, 3 * 2.0, 5):
+        ws, nws = _workspace(vat.device, "cn_coatt_f8_train_workspace_bytes", n, hw, dtype=torch.uint8)
+        nv.call("cn_coatt_f8_train_fwd", *_coatt_args(vat, va, vb, n, hw, za, zb), lse_a.data_ptr(),
+                lse_b.data_ptr(), q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), c, nv.ptr(ws), nws,
+                nv.stream())
     return tuple(q)
 
 
 def coatt_flash_fwd(vat, va, vb, n, hw, za, zb, lse_a, lse_b):
     """Training forward of both co-attention directions (S never in HBM) + the per-row
     log2-sum-exp2 normalisers [n, hw_pad(hw)] the backward recomputes P from."""
-    c = vat.shape[1]
-    ev = _prof_start(3 * 2.0 * n * hw * hw * c, ("coatt_flash_fwd", n, hw, c),
-                     (3 * n * hw * c + 2 * n * hw * c) * vat.element_size())
-    nws = int(nv.query("cn_coatt_fused_workspace_bytes", n, hw, 2))
-    ws = torch.empty((nws // 4,), dtype=torch.float32, device=vat.device) if nws else None
-    nv.call("cn_coatt_flash_fwd_ws", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), vb.data_ptr(),
-            ld(vb), n, hw, c, za.data_ptr(), zb.data_ptr(), ld(za), lse_a.data_ptr(),
-            lse_b.data_ptr(), nv.ptr(ws), nws, nv.stream())
-    _prof_end(ev)
+    with _profiled(_coatt_record, "coatt_flash_fwd", vat, n, hw, 3 * 2.0, 5):
+        ws, nws = _workspace(vat.device, "cn_coatt_fused_workspace_bytes", n, hw, 2, per=4)
+        nv.call("cn_coatt_flash_fwd_ws", *_coatt_args(vat, va, vb, n, hw, za, zb), lse_a.data_ptr(),
+                lse_b.data_ptr(), nv.ptr(ws), nws, nv.stream())
 
 
 def coatt_flash_bwd(vat, va, vb, wf, za, zb, lse_a, lse_b, dza, dzb, n, hw, dva=None,
@@ -759,32 +755,24 @@ def coatt_flash_bwd(vat, va, vb, wf, za, zb, lse_a, lse_b, dza, dzb, n, hw, dva=
     d0 = d1 = None
     if dza is not None:
         d0 = torch.empty((P,), dtype=torch.float32, device=dev)
-        nv.call("cn_rowdot", dtc(dza), dza.data_ptr(), ld(dza), za.data_ptr(), ld(za), P, c,
-                d0.data_ptr(), nv.stream())
+        nv.call("cn_rowdot", dtc(dza), *_mat(dza), *_mat(za), P, c, d0.data_ptr(), nv.stream())
     if dzb is not None:
         d1 = torch.empty((n * hwp,), dtype=torch.float32, device=dev)
-        nv.call("cn_rowdot_seg", dtc(dzb), dzb.data_ptr(), ld(dzb), zb.data_ptr(), ld(zb), P, c, hw,
-                hwp, d1.data_ptr(), nv.stream())
+        nv.call("cn_rowdot_seg", dtc(dzb), *_mat(dzb), *_mat(zb), P, c, hw, hwp, d1.data_ptr(), nv.stream())
     dvat = torch.empty((P, c), dtype=vat.dtype, device=dev)
     nterm = (dza is not None) + (dzb is not None)
-    ev = _prof_start((1 + nterm) * 2.0 * n * hw * hw * c, ("coatt_flash_bwd", n, hw, c),
-                     (2 + 2 * nterm) * P * c * vat.element_size())
-    # one workspace for the key-split partials of both kernels (they run one after the other)
-    nws = max(int(nv.query("cn_coatt_flash_bwd_workspace_bytes", n, hw)),
-              int(nv.query("cn_coatt_fused_workspace_bytes", n, hw, 1)) if dva is not None else 0)
-    ws = torch.empty((nws // 4,), dtype=torch.float32, device=dev) if nws else None
-    nv.call("cn_coatt_flash_dvat_ws", vat.data_ptr(), ld(vat), va.data_ptr(), ld(va), nv.ptr(dza),
-            ld(dza) if dza is not None else c, vb.data_ptr(), ld(vb), nv.ptr(dzb),
-            ld(dzb) if dzb is not None else c, lse_a.data_ptr(), nv.ptr(d0), lse_b.data_ptr(),
-            nv.ptr(d1), n, hw, c, dvat.data_ptr(), ld(dvat), 0, nv.ptr(ws), nws, nv.stream())
-    _prof_end(ev)
+    with _profiled(_coatt_record, "coatt_flash_bwd", vat, n, hw, (1 + nterm) * 2.0, 2 + 2 * nterm):
+        # one workspace for the key-split partials of both kernels (they run one after the other)
+        ws, nws = _workspace(dev, max(int(nv.query("cn_coatt_flash_bwd_workspace_bytes", n, hw)),
+                                      int(nv.query("cn_coatt_fused_workspace_bytes", n, hw, 1))
+                                      if dva is not None else 0), per=4)
+        nv.call("cn_coatt_flash_dvat_ws", *_mat(vat), *_mat(va), *_mat(dza, c), *_mat(vb),
+                *_mat(dzb, c), lse_a.data_ptr(), nv.ptr(d0), lse_b.data_ptr(), nv.ptr(d1), n, hw, c,
+                *_mat(dvat), 0, nv.ptr(ws), nws, nv.stream())
     if dva is not None and dzb is not None:
-        ev = _prof_start(2.0 * n * hw * hw * c, ("coatt_flash_bwd", n, hw, c),
-                         3 * P * c * vat.element_size())
-        nv.call("cn_coatt_flash_pv_ws", vat.data_ptr(), ld(vat), vb.data_ptr(), ld(vb), dzb.data_ptr(),
-                ld(dzb), lse_b.data_ptr(), n, hw, c, dva.data_ptr(), ld(dva), int(dva_accumulate),
-                nv.ptr(ws), nws, nv.stream())
-        _prof_end(ev)
+        with _profiled(_coatt_record, "coatt_flash_bwd", vat, n, hw, 2.0, 3):
+            nv.call("cn_coatt_flash_pv_ws", *_mat(vat), *_mat(vb), *_mat(dzb), lse_b.data_ptr(), n, hw, c,
+                    *_mat(dva), int(dva_accumulate), nv.ptr(ws), nws, nv.stream())
     return dvat
 
 
@@ -798,8 +786,7 @@ def _nsplit_eff(k, nsplit, dt):
 
 # ---- batch norm -------------------------------------------------------------------------------
 def _ws(dtype, p, c, device, nseg=1):
-    n = nv.query("cn_bn_workspace_floats", nv.dtype_code(dtype), p, c, nseg)
-    return torch.empty((max(int(n), 1),), dtype=torch.float32, device=device)
+    return _workspace(device, "cn_bn_workspace_floats", nv.dtype_code(dtype), p, c, nseg, floor=1)[0]
 
 
 def bn_stats(x, bn, training, nseg=1, count_update=True):
@@ -815,7 +802,7 @@ def bn_stats(x, bn, training, nseg=1, count_update=True):
     if training:
         _check_train_rows(p, 1, c)
         ws = _ws(x.dtype, p, c, x.device, nseg)
-        nv.call("cn_bn_stats", dtc(x), x.data_ptr(), ld(x), p, nseg, c, mean.data_ptr(),
+        nv.call("cn_bn_stats", dtc(x), *_mat(x), p, nseg, c, mean.data_ptr(),
                 invstd.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
                 _momentum(bn), float(bn.eps), ws.data_ptr(), nv.stream())
         if count_update:
@@ -852,9 +839,8 @@ def _bn_apply_args(x, stats, bn, act, prelu, res, xr, rstats, rbn, nseg):
     p, c = x.shape
     g, b = _affine(bn)
     rg, rb = _affine(rbn) if rbn is not None else (None, None)
-    return (dtc(x), x.data_ptr(), ld(x), p // nseg, nseg, c, stats[0].data_ptr(), stats[1].data_ptr(),
-            nv.ptr(g), nv.ptr(b), nv.ptr(res), ld(res) if res is not None else 0,
-            nv.ptr(xr), ld(xr) if xr is not None else 0, nv.ptr(rstats[0] if rstats else None),
+    return (dtc(x), *_mat(x), p // nseg, nseg, c, stats[0].data_ptr(), stats[1].data_ptr(), nv.ptr(g),
+            nv.ptr(b), *_mat(res, 0), *_mat(xr, 0), nv.ptr(rstats[0] if rstats else None),
             nv.ptr(rstats[1] if rstats else None), nv.ptr(rg), nv.ptr(rb), act, nv.ptr(prelu))
 
 
@@ -870,8 +856,8 @@ def bn_apply(x, stats, bn, act=0, prelu=None, res=None, xr=None, rstats=None, rb
     if out is None:
         out = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device)
     nv.call("cn_bn_apply_ex", *_bn_apply_args(x, stats, bn, act, prelu, res, xr, rstats, rbn, nseg),
-            out.data_ptr(), ld(out), nv.ptr(out8), ld(out8) if out8 is not None else 0,
-            nv.ptr(qstate), nv.ptr(mask), mask.stride(0) if mask is not None else 0, nv.stream())
+            *_mat(out), *_mat(out8, 0), nv.ptr(qstate), nv.ptr(mask),
+            mask.stride(0) if mask is not None else 0, nv.stream())
     return out
 
 
@@ -883,8 +869,7 @@ def bn_apply_q8(x, stats, bn, qstate, act=0, prelu=None, res=None, xr=None, rsta
     if out8 is None:
         out8 = torch.empty(tuple(x.shape), dtype=torch.uint8, device=x.device)
     nv.call("cn_bn_apply_q8", *_bn_apply_args(x, stats, bn, act, prelu, res, xr, rstats, rbn, nseg),
-            nv.ptr(out), ld(out) if out is not None else 0, out8.data_ptr(), ld(out8),
-            qstate.data_ptr(), nv.stream())
+            *_mat(out, 0), *_mat(out8), qstate.data_ptr(), nv.stream())
     return out, out8
 
 
@@ -907,11 +892,11 @@ def bn_bwd(x, dy, y, stats, bn, act=0, prelu=None, want_dx=True, dx=None, dres=N
         dx = torch.empty((p, c), dtype=x.dtype, device=x.device)
     ws = _ws(x.dtype, p, c, x.device)
     g, b = _affine(bn)
-    nv.call("cn_bn_bwd", dtc(x), x.data_ptr(), ld(x), dy.data_ptr(), ld(dy), nv.ptr(y),
-            (y.stride(0) if act == 4 else ld(y)) if y is not None else 0, p, c, stats[0].data_ptr(), stats[1].data_ptr(), nv.ptr(g),
-            nv.ptr(b), act, nv.ptr(prelu), dgamma.data_ptr(), dbeta.data_ptr(), nv.ptr(dpc),
-            nv.ptr(dx), ld(dx) if dx is not None else 0, nv.ptr(dres),
-            ld(dres) if dres is not None else 0, ws.data_ptr(), nv.stream())
+    # act 4: y is the bit mask, whose row stride is taken as it is (bytes)
+    ym = (y.data_ptr(), y.stride(0)) if act == 4 and y is not None else _mat(y, 0)
+    nv.call("cn_bn_bwd", dtc(x), *_mat(x), *_mat(dy), *ym, p, c, stats[0].data_ptr(), stats[1].data_ptr(),
+            nv.ptr(g), nv.ptr(b), act, nv.ptr(prelu), dgamma.data_ptr(), dbeta.data_ptr(), nv.ptr(dpc),
+            *_mat(dx, 0), *_mat(dres, 0), ws.data_ptr(), nv.stream())
     if dpc is not None:  # per-channel partials -> the single PReLU weight (fixed order)
         if dprelu is None:
             dprelu = torch.empty((1,), dtype=torch.float32, device=x.device)
@@ -920,6 +905,6 @@ def bn_bwd(x, dy, y, stats, bn, act=0, prelu=None, want_dx=True, dx=None, dres=N
 
 
 def cast_copy(src, dst, accumulate=False):
-    nv.call("cn_cast2d", dtc(src), dtc(dst), src.data_ptr(), ld(src), src.shape[0], src.shape[1],
-            dst.data_ptr(), ld(dst), int(accumulate), nv.stream())
+    nv.call("cn_cast2d", dtc(src), dtc(dst), *_mat(src), src.shape[0], src.shape[1], *_mat(dst),
+            int(accumulate), nv.stream())
     return dst
