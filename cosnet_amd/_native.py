@@ -18,6 +18,9 @@ DT_F32 = 0
 DT_BF16 = 1
 
 HEADER = os.path.join(_HERE, "..", "include", "cosnet_hip.h")
+# inference extensions: launches that replace a pair of reference calls (conv2d + eval BatchNorm2d);
+# a table of their own, so the core header's entry points stay the set its tests pin
+HEADER_INFER = os.path.join(_HERE, "..", "include", "cosnet_hip_infer.h")
 
 
 class NativeError(RuntimeError):
@@ -54,6 +57,7 @@ def signatures(header_text):
 
 
 _sigs = None
+_ext_sigs = None
 
 
 def _signatures():
@@ -62,6 +66,19 @@ def _signatures():
         with open(HEADER) as fh:
             _sigs = signatures(fh.read())
     return _sigs
+
+
+def _extension_signatures():
+    global _ext_sigs
+    if _ext_sigs is None:
+        with open(HEADER_INFER) as fh:
+            _ext_sigs = signatures(fh.read())
+    return _ext_sigs
+
+
+def _signature(name):
+    """The prototype of one entry point, from whichever header declares it."""
+    return _signatures().get(name) or _extension_signatures()[name]
 
 
 _lib = None
@@ -75,7 +92,7 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise NativeError("libcosnet_hip.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args, _) in _signatures().items():
+    for name, (res, args, _) in list(_signatures().items()) + list(_extension_signatures().items()):
         # an A/B build of an older tree (COSNET_HIP_LIB) may lack the newest entry points; the
         # in-tree product library must export every one
         if os.environ.get("COSNET_HIP_LIB") and not hasattr(lib, name):
@@ -89,7 +106,8 @@ def load():
 
 HASHED_SOURCES = ["gemm.hip", "gemm_ws.hip", "conv.hip", "bn.hip", "ew.hip", "coatt.hip", "coatt_fused.hip",
                   "coatt_q48.hip", "coatt_flash.hip", "coatt_f8.hip", "fp8.hip", "frames.hip", "eval.hip",
-                  "common.h", "gemm.h", "gemm_dev.h", "coatt_fused.h", "../../include/cosnet_hip.h"]   # csrc/Makefile HASHED, same order
+                  "common.h", "gemm.h", "gemm_dev.h", "coatt_fused.h", "../../include/cosnet_hip.h",
+                  "../../include/cosnet_hip_infer.h"]   # csrc/Makefile HASHED, same order
 
 
 def source_hash():
@@ -117,6 +135,11 @@ def exported_symbols():
     return sorted(_signatures())
 
 
+def extension_symbols():
+    """The entry points of include/cosnet_hip_infer.h (exported_symbols() stays the core header's)."""
+    return sorted(_extension_signatures())
+
+
 _ERR = {-1: "shape", -2: "alignment", -3: "unsupported", -4: "hip runtime"}
 
 
@@ -126,7 +149,7 @@ def call(name, *args):
         rc = getattr(load(), name)(*args)
     except ctypes.ArgumentError as e:   # "argument 9: TypeError: ..." -> name the C parameter
         i = int(re.match(r"argument (\d+)", str(e)).group(1))
-        raise NativeError("%s: argument %d (%s): %s" % (name, i, _signatures()[name][2][i - 1], e)) from e
+        raise NativeError("%s: argument %d (%s): %s" % (name, i, _signature(name)[2][i - 1], e)) from e
     if rc != 0:
         raise NativeError("%s failed: %s (%d)" % (name, _ERR.get(rc, "hipError"), rc))
     return rc

@@ -9,6 +9,7 @@
 // constants live in registers) and walks rows with stride RPB * gridDim.y.
 #include "common.h"
 #include "../../include/cosnet_hip.h"
+#include "../../include/cosnet_hip_infer.h"
 
 namespace {
 
@@ -456,6 +457,24 @@ __global__ __launch_bounds__(256) void bn_apply_k(const T* __restrict__ x, long 
   if (y8) fp8_block_amax(qmax, qstate);
 }
 
+// ---- eval-mode fold table (include/cosnet_hip_infer.h) --------------------------------------
+// The per-channel affine bn_apply_k forms on every call, written once: invstd as bn_eval_params,
+// then sc / sf by bn_apply_k's own two source expressions, so a GEMM epilogue that runs
+// fmaf(c, scale, shift) computes bitwise what the apply computes from (mean, invstd, gamma, beta).
+__global__ void bn_fold_table_k(const float* rm, const float* rv, const float* gamma, const float* beta,
+                                int C, float eps, float* scale, float* shift) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  float sc = gamma ? gamma[c] : 1.f;
+  float sf = beta ? beta[c] : 0.f;
+  const float t0 = 1.0f / sqrtf(rv[c] + eps);
+  const float t1 = rm[c];
+  sc *= t0;
+  sf -= t1 * sc;
+  scale[c] = sc;
+  shift[c] = sf;
+}
+
 // ---- static-scale apply (inference, cosnet_amd/fp8_infer.py) --------------------------------
 // bn_apply_k's arithmetic with the e4m3 image of the fp32 activation written under a FROZEN
 // scale: qstate is only read, so there is no amax, no atomic and no block-wide reduction, and the
@@ -871,6 +890,16 @@ extern "C" int cn_bn_bwd_apply(int dtype, const void* x, long long ldx, const vo
 extern "C" int cn_bn_eval_params(const float* run_mean, const float* run_var, int C, float eps,
                                  float* mean, float* invstd, hipStream_t st) {
   hipLaunchKernelGGL(bn_eval_params, dim3((C + 255) / 256), dim3(256), 0, st, run_mean, run_var, C, eps, mean, invstd);
+  CN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int cn_bn_fold_table(const float* run_mean, const float* run_var, const float* gamma,
+                                const float* beta, int C, float eps, float* scale, float* shift,
+                                hipStream_t st) {
+  if (C < 1 || !run_mean || !run_var || !scale || !shift) return CN_ERR_SHAPE;
+  hipLaunchKernelGGL(bn_fold_table_k, dim3((C + 255) / 256), dim3(256), 0, st, run_mean, run_var, gamma,
+                     beta, C, eps, scale, shift);
   CN_CHECK_LAUNCH();
   return 0;
 }

@@ -7,6 +7,7 @@
 // builders take flags where the entries differ.
 #include "gemm.h"
 #include "../../include/cosnet_hip.h"
+#include "../../include/cosnet_hip_infer.h"
 
 static GemmArgs gemm_defaults() {
   GemmArgs a = {};
@@ -222,6 +223,96 @@ extern "C" int cn_conv_fwd_ws(int dtype, const void* x, long long ldx, int N, in
   if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(splitk_reduce_bf16_k, dim3((unsigned)nb), dim3(256), 0, st, ws, ns, a.slab, M,
                      Cout, bias, (bf16*)y, ldy);
+  CN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- forward conv with an eval-mode BatchNorm folded into its epilogue ----------------------
+// (include/cosnet_hip_infer.h).  The split-K reduce of the deep one-round shapes, with the folded
+// affine, the residual and the activation between the bias and the one rounding.
+__global__ __launch_bounds__(256) void splitk_reduce_affine_bf16_k(
+    const float* __restrict__ ws, int nsplit, long long slab, int M, int N,
+    const float* __restrict__ bias, const float* __restrict__ scale, const float* __restrict__ shift,
+    const bf16* __restrict__ res, long long ldr, int act, const float* __restrict__ prelu,
+    bf16* __restrict__ y, long long ldy) {
+  const int cpr = N / 8;
+  const long long total = (long long)M * cpr;
+  const float slope = act == 2 ? prelu[0] : 0.f;
+  for (long long t = blockIdx.x * 256ll + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+    const int r = (int)(t / cpr), c = (int)(t - (long long)r * cpr) * 8;
+    const float* p = ws + (long long)r * N + c;
+    f32x4 a0 = *(const f32x4*)p, a1 = *(const f32x4*)(p + 4);
+    for (int sp = 1; sp < nsplit; ++sp) {
+      a0 += *(const f32x4*)(p + sp * slab);
+      a1 += *(const f32x4*)(p + sp * slab + 4);
+    }
+    float f[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
+    if (bias) {
+#pragma unroll
+      for (int v = 0; v < 8; ++v) f[v] += bias[c + v];
+    }
+    const f32x4 s0 = *(const f32x4*)(scale + c), s1 = *(const f32x4*)(scale + c + 4);
+    const f32x4 h0 = *(const f32x4*)(shift + c), h1 = *(const f32x4*)(shift + c + 4);
+    float q[8];
+    if (res) Chunk<bf16>::unpack(*(const u32x4*)(res + (long long)r * ldr + c), q);
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+      float u = fmaf(f[v], v < 4 ? s0[v] : s1[v - 4], v < 4 ? h0[v] : h1[v - 4]);
+      if (res) u += q[v];
+      if (act == 1) u = fmaxf(u, 0.f);
+      else if (act == 2) u = u > 0.f ? u : slope * u;
+      f[v] = u;
+    }
+    *(u32x4*)(y + (long long)r * ldy + c) = Chunk<bf16>::pack(f);
+  }
+}
+
+extern "C" int cn_conv_fwd_affine(int dtype, const void* x, long long ldx, int N, int H, int W, int Cin,
+                                  const void* w, int Cout, int KH, int KW, int stride, int pad, int dil,
+                                  const float* bias, void* y, long long ldy, int OH, int OW,
+                                  const float* scale, const float* shift, const void* res,
+                                  long long ldr, int act, const float* prelu, float* ws,
+                                  size_t ws_floats, hipStream_t st) {
+  if (dtype != DT_BF16 && dtype != DT_F32) return CN_ERR_UNSUPPORTED;
+  if (!scale || !shift) return CN_ERR_SHAPE;
+  if (misaligned(scale) || misaligned(shift)) return CN_ERR_ALIGN;
+  if (act < 0 || act > 2 || (act == 2 && !prelu)) return CN_ERR_UNSUPPORTED;
+  int ns, ch;
+  const int M = N * OH * OW, K = KH * KW * Cin;
+  const bool split = ws && !misaligned(ws) && !misaligned(y) && ldy % 8 == 0 &&
+                     !(res && (misaligned(res) || ldr % 8)) &&
+                     fwd_split_plan(dtype, M, Cout, K, &ns, &ch) && ws_floats >= (size_t)ns * M * Cout;
+  GemmArgs a;
+  int la;
+  if (!split) {
+    int rc = conv_fwd_args(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, bias, y,
+                           ldy, OH, OW, a, la);
+    if (rc) return rc;
+    a.st_mode = 4;
+    a.br_gamma = scale;
+    a.br_beta = shift;
+    a.br_x = res;
+    a.br_ldx = ldr;
+    a.act = act;
+    a.prelu = prelu;
+    return cn_gemm_dispatch(a, dtype, dtype == DT_F32, la, L_KC_DENSE, 1, st);
+  }
+  // as cn_conv_fwd_ws: fp32 slabs [M][Cout] into ws; bias, affine, residual and activation in the reduce
+  int rc = conv_fwd_args(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, nullptr, ws,
+                         Cout, OH, OW, a, la);
+  if (rc) return rc;
+  a.c_mode = 3;
+  a.nsplit = ns;
+  a.k_chunk = ch;
+  a.slab = (long long)M * Cout;
+  a.cfg = 20;
+  rc = cn_gemm_dispatch(a, dtype, 1, la, L_KC_DENSE, 1, st);
+  if (rc) return rc;
+  const long long total = (long long)M * (Cout / 8);
+  long long nb = (total + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(splitk_reduce_affine_bf16_k, dim3((unsigned)nb), dim3(256), 0, st, ws, ns, a.slab,
+                     M, Cout, bias, scale, shift, (const bf16*)res, ldr, act, prelu, (bf16*)y, ldy);
   CN_CHECK_LAUNCH();
   return 0;
 }

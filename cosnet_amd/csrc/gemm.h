@@ -67,6 +67,10 @@ struct GemmArgs {
   //  st_mode 2: BN backward reduce of the stored C (= dy of a BN + ReLU whose pre-BN input is
   //             br_x): dz = dy * (br_x * k1 + sf > 0), xh = (br_x - mu) * is;
   //             planes [sum dz, sum dz * xh].  k1 = gamma * is, sf = beta - mu * k1.
+  //  st_mode 4: eval-mode BN folded into a forward conv (cn_conv_fwd_affine; no statistics, no
+  //             grouped launch): C = act(fma(acc + bias, br_gamma[n], br_beta[n]) + br_x[m][n]),
+  //             br_gamma / br_beta = the folded scale / shift, br_x / br_ldx = the residual rows
+  //             (C's type, nullable), act / prelu below.
   int st_mode;
   float* st_ws;
   long long st_plane;
@@ -77,6 +81,8 @@ struct GemmArgs {
   GemmGroup grp;
   int wt;                      // C stores: 4 non-temporal, 0 plain (other: write-through, sc1);
                                // set by cn_gemm_dispatch
+  int act;                     // st_mode 4: 0 none, 1 ReLU, 2 PReLU with the slope prelu[0]
+  const float* prelu;
 };
 
 int cn_gemm_dispatch(const GemmArgs& a, int dtype, int c_f32, int la, int lb, int batch, hipStream_t st);

@@ -522,15 +522,16 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
   constexpr int RPP = NT / GPR;          // rows per pass
   constexpr int IT = HR / RPP;           // rows per thread per pass
   static_assert(IT * RPP == HR, "epilogue rows per pass must be a multiple of the row stride");
-  constexpr int smode = EPI == 3 ? 0 : EPI;   // BN epilogue (compile-time: its registers would
-                                              // otherwise cost every plain GEMM occupancy)
+  constexpr int smode = (EPI == 3 || EPI == 4) ? 0 : EPI;   // BN epilogue (compile-time: its registers
+                                              // would otherwise cost every plain GEMM occupancy)
   constexpr bool PFC = EPI == 3;
+  constexpr bool AFF = EPI == 4;              // eval-mode BN fold (st_mode 4, gemm.h)
   constexpr int PQ = (int)sizeof(CT) / 2;     // 16-B chunks per 8 elements of C
   static_assert(!PFC || sizeof(CT) == 2, "EPI 3: bf16 C");
   const int c0t = (tid % GPR) * 8;            // this thread's columns within the tile (fixed)
   CT* Cb = (p.ngroup ? (CT*)p.grp.C[batch] : (CT*)p.C + (long long)batch * p.c_bs) +
            (p.c_mode == 3 ? (long long)split * p.slab : 0);
-  u32x4 xnx[(smode == 2 || PFC) ? IT * PQ : 1];   // the next staging pass's rows
+  u32x4 xnx[(smode == 2 || PFC || AFF) ? IT * PQ : 1];   // the next staging pass's rows
   // write-through C stores (p.wt): the block's rows from its first one, 32-bit offsets
   const __amdgpu_buffer_rsrc_t crs = buf_rsrc(Cb + (long long)m0 * p.ldc);
   auto epi_fetch = [&](int pass) {
@@ -547,14 +548,32 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
         const CT* dst = Cb + (long long)row * p.ldc + col;
         const bool ok = row < p.M && col + 8 <= p.N && ((uintptr_t)dst % 16 == 0);
         xnx[it] = ok ? *(const u32x4*)dst : u32x4{0u, 0u, 0u, 0u};
+      } else if constexpr (AFF) {
+        // the residual rows (null: none); a row the 16-byte loads cannot take (the tile's ragged
+        // edge, a misaligned view) is read element-wise by the store loop instead
+        const CT* src = (const CT*)p.br_x + (long long)row * p.br_ldx + col;
+        const bool ok = p.br_x && row < p.M && col + 8 <= p.N && ((uintptr_t)src % 16 == 0);
+#pragma unroll
+        for (int q = 0; q < PQ; ++q) xnx[it * PQ + q] = ok ? ((const u32x4*)src)[q] : u32x4{0u, 0u, 0u, 0u};
       }
     }
   };
   // EARLY: the prefetch registers stay live across the K loop -- only where that costs no spill
   // (tiles without the 128-VGPR occupancy bound of the 2-stage BN-epilogue kernels and below
   // 256 x 256, whose accumulators fill the register file; tools/kernel_resources.py checks)
-  constexpr bool EARLY = PFC || (smode == 2 && S >= 3 && BM * BN <= 128 * 128);
+  // (AFF: every tile but the 256 x 256 ping-pong tile on the per-thread-pointer gather, which spills)
+  constexpr bool EARLY = PFC || (AFF && !(LA == L_KC_CONV_G && BM * BN == 256 * 256 && PP == 1)) ||
+                         (smode == 2 && S >= 3 && BM * BN <= 128 * 128);
   float bk1[8], bsf[8], bmu[8];
+  float fsc[8], fsh[8];   // AFF: this thread's eight folded scale / shift values
+  auto epi_fold = [&]() {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int c = n0 + c0t + e;
+      fsc[e] = c < p.N ? p.br_gamma[c] : 0.f;
+      fsh[e] = c < p.N ? p.br_beta[c] : 0.f;
+    }
+  };
   auto epi_affine = [&]() {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -570,6 +589,7 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
   };
   if constexpr (EARLY) {
     if constexpr (smode == 2) epi_affine();
+    if constexpr (AFF) epi_fold();
     epi_fetch(0);
   }
 
@@ -811,17 +831,18 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
   int segA_end = 0x7fffffff;
   if constexpr (smode == 1) segA_end = (m0 / p.st_seg_rows + 1) * p.st_seg_rows;
   if constexpr (smode == 2 && !EARLY) epi_affine();
+  if constexpr (AFF && !EARLY) epi_fold();
 #pragma unroll 1
   for (int pass = 0; pass < BM / HR; ++pass) {
     // EARLY: this pass's rows were prefetched (before the K loop / during the previous pass) and
     // the next pass's loads go out now.  Otherwise this pass's loads go out now, in flight while
     // the accumulators are staged through LDS.
-    u32x4 xpf[(smode == 2 || PFC) ? IT * PQ : 1];
+    u32x4 xpf[(smode == 2 || PFC || AFF) ? IT * PQ : 1];
     if constexpr (EARLY) {
 #pragma unroll
       for (int i = 0; i < IT * PQ; ++i) xpf[i] = xnx[i];
       if (pass + 1 < BM / HR) epi_fetch(pass + 1);
-    } else if constexpr (smode == 2) {
+    } else if constexpr (smode == 2 || AFF) {
       epi_fetch(pass);
 #pragma unroll
       for (int i = 0; i < IT * PQ; ++i) xpf[i] = xnx[i];
@@ -870,6 +891,28 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
       if (bias) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += (col + e < p.N) ? bias[col + e] : 0.f;
+      }
+      if constexpr (AFF) {   // t = fma(acc + bias, scale, shift) + res, then the activation
+        float q[8];
+        const CT* rs = (const CT*)p.br_x + (long long)row * p.br_ldx + col;
+        if (p.br_x) {
+          if (col + 8 <= p.N && ((uintptr_t)rs % 16 == 0)) {   // prefetched (epi_fetch's condition)
+            if constexpr (sizeof(CT) == 2) Chunk<bf16>::unpack(xpf[it], q);
+            else { *(u32x4*)&q[0] = xpf[2 * it]; *(u32x4*)&q[4] = xpf[2 * it + 1]; }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) q[e] = (col + e < p.N) ? tof(rs[e]) : 0.f;
+          }
+        }
+        const float slope = p.act == 2 ? p.prelu[0] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float t = fmaf(v[e], fsc[e], fsh[e]);
+          if (p.br_x) t += q[e];
+          if (p.act == 1) t = fmaxf(t, 0.f);
+          else if (p.act == 2) t = t > 0.f ? t : slope * t;
+          v[e] = t;
+        }
       }
       if (cmode == 1) {
 #pragma unroll
@@ -1240,7 +1283,8 @@ static bool ws_heuristic(const GemmArgs& a) {
 static bool ws_eligible(const GemmArgs& a, int dtype, int c_f32, int la, int lb, int batch) {
   if (!g_ws_mode || g_force_cfg >= 0 || a.cfg >= 0) return false;
   if (dtype != DT_BF16 || c_f32 || la != L_KC_DENSE || lb != L_KC_DENSE) return false;
-  if (batch != 1 || a.nsplit != 1 || a.row_map || a.ngroup || a.st_mode) return false;
+  if (batch != 1 || a.nsplit != 1 || a.row_map || a.ngroup || (a.st_mode && a.st_mode != 4)) return false;
+  if (a.st_mode == 4 && a.c_mode != 0) return false;   // the eval-mode BN fold stores
   if ((a.c_mode != 0 && a.c_mode != 2) || a.bias || a.alpha != 1.f || a.scale_a || a.scale_b) return false;
   if (!cn_gemm_ws_supports(a)) return false;
   return g_ws_mode >= 2 || ws_heuristic(a);
@@ -1294,13 +1338,17 @@ int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb,
     if ((batch != 1 && !(a.ngroup == batch && a.st_mode == 1)) || a.nsplit != 1 || a.row_map || a.c_mode ||
         lb != L_KC_DENSE || (la != L_KC_DENSE && la != L_KC_CONV && la != L_KC_CONV_G))
       return CN_ERR_UNSUPPORTED;
+    if (a.st_mode == 4 && (a.ngroup || c_f32 != (dtype == DT_F32) || !a.br_gamma || !a.br_beta ||
+                           a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu)))
+      return CN_ERR_UNSUPPORTED;
+    if (a.st_mode < 1 || a.st_mode == 3 || a.st_mode > 4) return CN_ERR_UNSUPPORTED;
 #define CN_EPI(T_, M_) \
     return la == L_KC_DENSE ? launch_epi<T_, L_KC_DENSE, M_>(a, batch, st) : \
            la == L_KC_CONV ? launch_epi<T_, L_KC_CONV, M_>(a, batch, st) : launch_epi<T_, L_KC_CONV_G, M_>(a, batch, st)
     if (dtype == DT_BF16) {
-      if (a.st_mode == 1) CN_EPI(bf16, 1); else CN_EPI(bf16, 2);
+      if (a.st_mode == 1) CN_EPI(bf16, 1); else if (a.st_mode == 2) CN_EPI(bf16, 2); else CN_EPI(bf16, 4);
     } else {
-      if (a.st_mode == 1) CN_EPI(float, 1); else CN_EPI(float, 2);
+      if (a.st_mode == 1) CN_EPI(float, 1); else if (a.st_mode == 2) CN_EPI(float, 2); else CN_EPI(float, 4);
     }
 #undef CN_EPI
   }

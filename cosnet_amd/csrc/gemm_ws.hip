@@ -48,6 +48,10 @@ struct WsArgs {
   int nslices;   // BN-column slices of B
   int wpx;       // M walkers per XCD (each walker = nslices blocks, one per slice)
   int wt;        // C store policy (GemmArgs::wt)
+  // FOLD (eval-mode BN fold, GemmArgs st_mode 4): C = act(fma(acc, scale[n], shift[n]) + res[m][n])
+  const bf16* res; long long ldr;   // residual rows (FOLD 2)
+  const float* scale; const float* shift;
+  int act;       // 0 none, 1 ReLU
 };
 
 __device__ __forceinline__ u32x4 load16_asm(const void* p) {
@@ -69,10 +73,14 @@ __device__ __forceinline__ void wait_keep(u32x4 (&x)[N]) {
 }
 
 // KT = K / 64 k-tiles; BM x BN block tile, WM x WN waves; MODE2: read-add-store (c_mode 2);
-// BREG: B fragments in registers.
+// BREG: B fragments in registers; FOLD: the eval-mode BN fold before the one rounding -- 1 the
+// per-column affine and the activation, 2 also the residual rows, which take the old-C rows'
+// prefetch slots (as many loads per tile, issued as unconditionally: the counted waits are MODE2's).
 // LDS: [B slice: KT x BN x 128 B][A ring: 2 x KT x BM x 128 B][per-wave fp32 staging patches].
-template <int KT, int BM, int BN, int WM, int WN, bool MODE2, bool BREG>
+template <int KT, int BM, int BN, int WM, int WN, bool MODE2, bool BREG, int FOLD = 0>
 __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_ws_kernel(WsArgs p) {
+  static_assert(!(MODE2 && FOLD), "the fold stores, it does not accumulate");
+  constexpr bool PRE = MODE2 || FOLD == 2;   // rows prefetched under the counted wait
   constexpr int NT = WM * WN * 64;
   constexpr int BBYTES = KT * BN * 128, ASTG = KT * BM * 128;
   constexpr int TM = BM / WM, TN = BN / WN;   // wave tile
@@ -105,6 +113,19 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_ws_kernel(WsArgs p) {
   const int r1 = min(p.M, (int)((long long)m16 * (walker + 1) / nwalk) * 16);
   if (r0 >= r1) return;
   const int ntiles = (r1 - r0 + BM - 1) / BM;
+
+  // FOLD: this lane's eight scale / shift values (its columns are fixed for the launch), loaded
+  // before any LDS-DMA is in flight
+  float fsc[FOLD ? 8 : 1], fsh[FOLD ? 8 : 1];
+  if constexpr (FOLD != 0) {
+    const int fc = n0 + wn * TN + (lane % (TN / 8)) * 8;
+    const bool in = fc < p.N;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 s0 = in ? *(const f32x4*)(p.scale + fc) : z, s1 = in ? *(const f32x4*)(p.scale + fc + 4) : z;
+    const f32x4 h0 = in ? *(const f32x4*)(p.shift + fc) : z, h1 = in ? *(const f32x4*)(p.shift + fc + 4) : z;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { fsc[e] = s0[e]; fsc[4 + e] = s1[e]; fsh[e] = h0[e]; fsh[4 + e] = h1[e]; }
+  }
 
   char* Bs = smem;
   char* As = smem + BBYTES;
@@ -140,19 +161,21 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_ws_kernel(WsArgs p) {
   // epilogue geometry: lane -> 8 columns (lane % GPR) of rows lane / GPR + RPP it of the wave tile
   const int erow = wm * TM + lane / GPR, ecol = n0 + wn * TN + (lane % GPR) * 8;
   const bool col_ok = ecol < p.N;   // N % 8 == 0: a column group is whole or absent
-  u32x4 xnx[MODE2 ? IT : 1], xpf[MODE2 ? IT : 1];
-  auto fetch_c = [&](int t) {   // old C rows of tile t (always IT loads)
+  u32x4 xnx[PRE ? IT : 1], xpf[PRE ? IT : 1];
+  const bf16* const pre_base = FOLD == 2 ? p.res : p.C;
+  const long long pre_ld = FOLD == 2 ? p.ldr : p.ldc;
+  auto fetch_c = [&](int t) {   // old C (FOLD 2: residual) rows of tile t (always IT loads)
     const int m0 = r0 + t * BM;
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
       const int row = m0 + erow + it * RPP;
-      const bf16* src = (row < r1 && col_ok) ? p.C + (long long)row * p.ldc + ecol : p.C;
+      const bf16* src = (row < r1 && col_ok) ? pre_base + (long long)row * pre_ld + ecol : pre_base;
       xnx[it] = load16_asm(src);
     }
   };
   issue_a(0, As);
-  if constexpr (MODE2) fetch_c(0);
-  wait_keep<0, MODE2>(xnx);
+  if constexpr (PRE) fetch_c(0);
+  wait_keep<0, PRE>(xnx);
   raw_barrier();
 
   // BREG: the wave's B fragments (its TN columns over the whole K) live in registers for the
@@ -196,6 +219,16 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_ws_kernel(WsArgs p) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += q[e];
       }
+      if constexpr (FOLD != 0) {   // gemm_kernel's EPI 4 arithmetic
+        float q[8];
+        if constexpr (FOLD == 2) Chunk<bf16>::unpack(xpf[it], q);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float u = fmaf(v[e], fsc[e], fsh[e]);
+          if constexpr (FOLD == 2) u += q[e];
+          v[e] = p.act == 1 ? fmaxf(u, 0.f) : u;
+        }
+      }
       const int row = erow + it * RPP;   // within the tile
       const unsigned off = (m0 + row < r1 && col_ok) ? (unsigned)(((long long)row * p.ldc + ecol) * 2) : BUF_OOB;
       __builtin_amdgcn_raw_buffer_store_b128(Chunk<bf16>::pack(v), rc, (int)off, 0, AUX);
@@ -206,14 +239,14 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_ws_kernel(WsArgs p) {
 #pragma unroll 1
   for (int t = 0; t < ntiles; ++t) {
     char* cur = As + (t & 1) * ASTG;
-    if constexpr (MODE2) {
+    if constexpr (PRE) {
 #pragma unroll
       for (int it = 0; it < IT; ++it) xpf[it] = xnx[it];
     }
     // the other stage held tile t-1: every wave passed the barrier that ended it
     if (t + 1 < ntiles) {
       issue_a(t + 1, As + ((t + 1) & 1) * ASTG);
-      if constexpr (MODE2) fetch_c(t + 1);
+      if constexpr (PRE) fetch_c(t + 1);
     }
     f32x4 acc[RM][RN];
 #pragma unroll
@@ -244,7 +277,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_ws_kernel(WsArgs p) {
     else epilogue(t, std::integral_constant<int, 0>{}, acc);
     if (t + 1 < ntiles) {
       // tile t+1's A (and old C) are older than tile t's IT stores: leave only those in flight
-      wait_keep<IT, MODE2>(xnx);
+      wait_keep<IT, PRE>(xnx);
       raw_barrier();
     }
   }
@@ -259,6 +292,9 @@ int launch_ws(const GemmArgs& a, int cus, int cap, hipStream_t st) {
   w.C = (bf16*)a.C; w.ldc = a.ldc;
   w.nslices = (a.N + BN - 1) / BN;
   w.wt = a.wt;
+  w.res = (const bf16*)a.br_x; w.ldr = a.br_ldx;
+  w.scale = a.br_gamma; w.shift = a.br_beta;
+  w.act = a.act;
   const int per_xcd = cus / 8;
   // no more walkers than 16-row granules of M
   const int want = (int)((((long long)a.M + 15) / 16 + 7) / 8);
@@ -266,7 +302,11 @@ int launch_ws(const GemmArgs& a, int cus, int cap, hipStream_t st) {
   if (cap > 0) w.wpx = std::min(w.wpx, cap);
   if (w.wpx < 1) return CN_ERR_UNSUPPORTED;
   const dim3 grid(8 * w.wpx * w.nslices), block(WM * WN * 64);
-  if (a.c_mode == 2)
+  if (a.st_mode == 4 && a.br_x)
+    hipLaunchKernelGGL((gemm_ws_kernel<KT, BM, BN, WM, WN, false, BREG, 2>), grid, block, 0, st, w);
+  else if (a.st_mode == 4)
+    hipLaunchKernelGGL((gemm_ws_kernel<KT, BM, BN, WM, WN, false, BREG, 1>), grid, block, 0, st, w);
+  else if (a.c_mode == 2)
     hipLaunchKernelGGL((gemm_ws_kernel<KT, BM, BN, WM, WN, true, BREG>), grid, block, 0, st, w);
   else
     hipLaunchKernelGGL((gemm_ws_kernel<KT, BM, BN, WM, WN, false, BREG>), grid, block, 0, st, w);
@@ -296,6 +336,10 @@ bool cn_gemm_ws_supports(const GemmArgs& a) {
   if (a.N % 8 || a.ldc % 8 || (uintptr_t)a.C % 16) return false;
   if (a.lda % 8 || a.ldb % 8 || (uintptr_t)a.A % 16 || (uintptr_t)a.B % 16) return false;
   if (256 * a.ldc * 2 >= 0x80000000ll) return false;   // 32-bit store offsets within a tile
+  if (a.st_mode == 4) {   // the fold: ReLU or none, 16-byte pieces of the tables and the residual rows
+    if (a.act == 2 || (uintptr_t)a.br_gamma % 16 || (uintptr_t)a.br_beta % 16) return false;
+    if (a.br_x && (a.br_ldx % 8 || (uintptr_t)a.br_x % 16)) return false;
+  }
   const int cus = device_cus();
   return cus >= 8 && (a.N + ws_bn(a.K) - 1) / ws_bn(a.K) <= cus / 8;
 }

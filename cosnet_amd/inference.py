@@ -22,6 +22,9 @@ def multi_reference_x1(model, target, target_depth, searches, search_depths):
         # features_nhwc is the per-module path: it would run bf16 convs without saying so
         raise RuntimeError("multi_reference_x1 does not run static fp8 encoders: use "
                            "segment_sequence (or set_fp8_static(None))")
+    if getattr(model, "bn_fold", None) is not None:
+        raise RuntimeError("multi_reference_x1 does not run the BN fold: use segment_sequence "
+                           "(or set_bn_fold(False))")
     model._set_dtype()
     target, target_depth, searches, search_depths = map(
         model._prep, (target, target_depth, searches, search_depths))
@@ -144,7 +147,8 @@ class FeatureBank:
         """rgbs [T,3,H,W], depths [T,1,H,W] (fp32 NCHW on the GPU): both encoders over chunks of
         encode_chunk frames, then the two similarity linears (and, coatt = "mxfp8", the MX images),
         once per frame.  On a model with static fp8 set (model.set_fp8_static) the encoders run
-        fp8_infer.encode_frames_static: e4m3 conv GEMMs on frozen scales; the bank stays bf16."""
+        fp8_infer.encode_frames_static: e4m3 conv GEMMs on frozen scales; the bank stays bf16.  On
+        a model with the BN fold set (model.set_bn_fold) they run bn_fold.encode_frames_folded."""
         if model.training:
             raise RuntimeError("FeatureBank.encode runs in eval mode (test.py:230)")
         if coatt not in cls.COATT:
@@ -163,6 +167,9 @@ class FeatureBank:
         if static:   # e4m3 conv GEMMs on frozen scales (cosnet_amd/fp8_infer.py); the bank stays bf16
             from .fp8_infer import encode_frames_static
             feats = lambda enc, x: encode_frames_static(enc, x)
+        elif getattr(model, "bn_fold", None) is not None:   # one launch per conv + eval BN pair
+            from .bn_fold import encode_frames_folded
+            feats = lambda enc, x: encode_frames_folded(enc, x)
         else:
             feats = lambda enc, x: enc.features_nhwc(x)
         for f0 in range(0, t, encode_chunk):

@@ -283,6 +283,45 @@ def conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=None, out=None):
     return out, g.oh, g.ow
 
 
+def _fwd_affine_record(tag, g, es, has_res):
+    """A forward conv with the eval-mode BN folded in: x and the weights read, the residual read if
+    there is one, y written once -- no raw conv output."""
+    fl, tg, nb = _fwd_record(tag, g, es, es)
+    return fl, tg, nb + (es * g.M * g.cout if has_res else 0)
+
+
+def conv_fwd_affine(x, n, h, w, wf, cout, k, stride, pad, dil, scale, shift, act=0, prelu=None, res=None,
+                    bias=None, out=None):
+    """y = act(fma(conv(x) + bias, scale, shift) + res) in one launch (cn_conv_fwd_affine): a conv
+    and the eval-mode BatchNorm behind it, scale / shift fp32 [cout] from bn_fold_table; act 0
+    none, 1 ReLU, 2 PReLU (prelu[0]); res a [M, cout] view of y's dtype.  x [n*h*w, >=cin] ->
+    (y [n*oh*ow, cout] or `out`, oh, ow); the raw conv output is never written."""
+    g, out, args = _fwd_conv(x, n, h, w, wf, cout, k, stride, pad, dil, bias, out, x.dtype)
+    if res is not None and (res.dtype != out.dtype or tuple(res.shape) != (g.M, cout)):
+        raise ValueError("conv_fwd_affine: res must be a [%d, %d] view of the output's dtype" % (g.M, cout))
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != cout or t.stride(0) != 1:
+            raise ValueError("conv_fwd_affine: scale / shift are fp32 [%d] arrays" % cout)
+    with _profiled(_fwd_affine_record, "fwd_affine", g, x.element_size(), res is not None):
+        nws = fwd_split_floats(x, g.M, cout, g.K)
+        nv.call("cn_conv_fwd_affine", dtc(x), *args, scale.data_ptr(), shift.data_ptr(), *_mat(res, 0),
+                int(act), nv.ptr(prelu), nv.ptr(_workspace(x.device, nws)[0]), nws, nv.stream())
+    return out, g.oh, g.ow
+
+
+def bn_fold_table(bn, out=None):
+    """(scale, shift) fp32 [C] of an eval-mode BatchNorm2d (cn_bn_fold_table): the affine bn_apply
+    forms from the running statistics on every call, written once.  `out`: a [2, C] fp32 tensor
+    to fill in place."""
+    c = bn.running_mean.shape[0]
+    if out is None:
+        out = torch.empty((2, c), dtype=torch.float32, device=bn.running_mean.device)
+    g, b = _affine(bn)
+    nv.call("cn_bn_fold_table", bn.running_mean.data_ptr(), bn.running_var.data_ptr(), nv.ptr(g), nv.ptr(b),
+            c, float(bn.eps), out[0].data_ptr(), out[1].data_ptr(), nv.stream())
+    return out[0], out[1]
+
+
 def fwd_split_floats(x, m, cout, kdim):
     """Workspace of the split-K forward (cn_conv_fwd_workspace_floats; 0: the shape does not split)."""
     return int(nv.query("cn_conv_fwd_workspace_floats", dtc(x), m, cout, kdim))

@@ -60,6 +60,7 @@ class RGBDSegmentation_RAA(nn.Module):
         self.compute_dtype = torch.bfloat16
         self.fp8 = None            # Fp8Context: e4m3 forward conv GEMMs in the encoders (configs[4])
         self.fp8_static = None     # Fp8Static: frozen-scale e4m3 encoders for inference (set_fp8_static)
+        self.bn_fold = None        # BnFold: eval-mode BN folded into the conv GEMMs (set_bn_fold)
         self.pair_encoder = True   # batch frames a and b through each encoder (encoder_fn.py)
         # depth encoder on a second stream (forward()); CN_CONCURRENT_ENCODERS=0 for A/B runs
         self.concurrent_encoders = os.environ.get("CN_CONCURRENT_ENCODERS", "1") != "0"
@@ -151,6 +152,8 @@ class RGBDSegmentation_RAA(nn.Module):
             raise ValueError("fp8 convs run inside the bf16 path")
         if on and getattr(self, "fp8_static", None) is not None:
             raise RuntimeError("set_fp8: static fp8 inference is set (set_fp8_static(None) first)")
+        if on and getattr(self, "bn_fold", None) is not None:
+            raise RuntimeError("set_fp8: the BN fold is set (set_bn_fold(False) first)")
         from .fp8 import Fp8Context
         self.fp8 = Fp8Context() if on else None
         self._fp8_depth = Fp8Context() if on else None
@@ -172,6 +175,8 @@ class RGBDSegmentation_RAA(nn.Module):
             raise ValueError("fp8 convs run inside the bf16 path")
         if getattr(self, "fp8", None) is not None:
             raise RuntimeError("set_fp8_static: delayed-scaling fp8 is set (set_fp8(False) first)")
+        if getattr(self, "bn_fold", None) is not None:
+            raise RuntimeError("set_fp8_static: the BN fold is set (set_bn_fold(False) first)")
         from .fp8_infer import Fp8Static
         if isinstance(calibration, Fp8Static):   # a state this model built before: switched back on
             st = calibration
@@ -182,6 +187,38 @@ class RGBDSegmentation_RAA(nn.Module):
         self.fp8_static = st
         self.encoder._cn_fp8_static = st.encoders["encoder"]
         self.depth_encoder._cn_fp8_static = st.encoders["depth_encoder"]
+        return self
+
+    def set_bn_fold(self, on=True):
+        """Eval-mode BatchNorm folded into the conv GEMMs for whole-sequence inference
+        (cosnet_amd/bn_fold.py): FeatureBank.encode / segment_sequence run both encoders with one
+        launch per conv + BN pair (cn_conv_fwd_affine; no raw conv output is written) and
+        head_a_indexed folds the two reduce convs' BNs.  The per-BN (scale, shift) tables are
+        built now and follow later changes of the BN tensors.  Needs eval mode; bf16 and fp32;
+        exclusive with set_fp8(True) and set_fp8_static.  False switches it off: the default
+        path is untouched; the built state (model.bn_fold) given back switches it on again
+        without rebuilding the tables."""
+        if not on:
+            self.bn_fold = None
+            for enc in (self.encoder, self.depth_encoder):
+                enc._cn_bn_fold = None
+            return self
+        if self.training:
+            raise RuntimeError("set_bn_fold: the BN fold uses running statistics (eval mode)")
+        if getattr(self, "fp8", None) is not None:
+            raise RuntimeError("set_bn_fold: delayed-scaling fp8 is set (set_fp8(False) first)")
+        if getattr(self, "fp8_static", None) is not None:
+            raise RuntimeError("set_bn_fold: static fp8 is set (set_fp8_static(None) first)")
+        from .bn_fold import BnFold
+        if isinstance(on, BnFold):   # a state this model built before: switched back on
+            st = on
+            if st.model() is not self:
+                raise ValueError("set_bn_fold: the fold tables were built for another model")
+        else:
+            st = BnFold(self)
+        self.bn_fold = st
+        self.encoder._cn_bn_fold = st.encoders["encoder"]
+        self.depth_encoder._cn_bn_fold = st.encoders["depth_encoder"]
         return self
 
     def _set_dtype(self):
@@ -206,6 +243,10 @@ class RGBDSegmentation_RAA(nn.Module):
             raise RuntimeError("static fp8 is an inference path of the feature bank "
                                "(inference.segment_sequence); set_fp8_static(None) to train or "
                                "to run the pair forward")
+        if getattr(self, "bn_fold", None) is not None:
+            raise RuntimeError("the BN fold is an inference path of the feature bank "
+                               "(inference.segment_sequence); set_bn_fold(False) to train or to "
+                               "run the pair forward")
         self._set_dtype()
         rgbs_a, rgbs_b, depths_a, depths_b = map(self._prep, (rgbs_a, rgbs_b, depths_a, depths_b))
         input_size = tuple(rgbs_a.shape[2:])
@@ -300,6 +341,7 @@ class RGBDSegmentation_RAA(nn.Module):
             raise RuntimeError("head_a_indexed is an inference path: eval mode under torch.no_grad()")
         if getattr(self, "fp8", None) is not None:
             raise RuntimeError("head_a_indexed: fp8 banks are not supported (set_fp8(False))")
+        fold = getattr(self, "bn_fold", None)   # set_bn_fold: the reduce conv and its BN in one launch
         self._set_dtype()
         t, h, w = bank.geo
         hw = h * w
@@ -341,6 +383,11 @@ class RGBDSegmentation_RAA(nn.Module):
                                      ((v, ia_h), (vt, ia_h), (v, ib_h)))
                 za = fn.coatt_a_materialised(vat_s, vb_s, p, hw)
                 cat = fn.GateCatFn.apply(za, va_s, gate.weight, gate.bias, False)
+            if fold is not None:
+                wf, _ = ops.WCACHE.get(reduce.weight, cat.dtype)
+                sc, sf = fold.head.get(bn)
+                zs.append(ops.conv_fwd_affine(cat, p, h, w, wf, reduce.weight.shape[0], 3, 1, 1, 1, sc, sf)[0])
+                continue
             zs.append(fn.BNFn.apply(fn.ConvFn.apply(cat, reduce.weight, None, geo, 3, 1, 1, 1),
                                     bn.weight, bn.bias, bn))
         z_a, dz_a = zs

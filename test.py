@@ -60,6 +60,9 @@ def get_arguments(argv=None):
     p.add_argument("--coatt", default="bf16", choices=["bf16", "mxfp8"],
                    help="--feature-bank: the bank's co-attention.  bf16 (default): the bf16 indexed kernel; "
                         "mxfp8: MX-fp8 images of the bf16 features, each frame quantised once per sequence")
+    p.add_argument("--fold-bn", action="store_true",
+                   help="--feature-bank (bf16 / fp32): every conv + eval-mode BatchNorm pair of the encoders and "
+                        "of the head's reduce convs as one launch (cosnet_amd/bn_fold.py)")
     p.add_argument("--fp8-calibration", default=None, metavar="FILE",
                    help="--dtype fp8: the calibration (JSON).  Loaded if the file exists; otherwise made "
                         "before evaluation from the first --fp8-calibration-frames test frames and written there")
@@ -71,6 +74,10 @@ def get_arguments(argv=None):
         p.error("--coatt mxfp8 needs --dtype bf16 (or fp8, whose features are bf16)")
     if args.dtype == "fp8" and not args.feature_bank:
         p.error("--dtype fp8 needs --feature-bank")
+    if args.fold_bn and not args.feature_bank:
+        p.error("--fold-bn needs --feature-bank")
+    if args.fold_bn and args.dtype == "fp8":
+        p.error("--fold-bn runs the bf16 / fp32 encoders (not --dtype fp8)")
     if args.dtype == "fp8" and args.fp8_calibration_frames < 1:
         p.error("--fp8-calibration-frames must be at least 1")
     if args.dtype != "fp8" and args.fp8_calibration:
@@ -136,6 +143,8 @@ def main(argv=None):
         print("no pretrained_params given: seeded initialisation (scores are meaningless)")
     model.eval()
     model.to(dev)
+    if args.fold_bn:
+        model.set_bn_fold()
 
     out_dir = None
     if str(args.save_seg_img) not in ("False", "0", ""):

@@ -58,7 +58,12 @@ def parse():
     ap.add_argument("--pair-chunk", type=int, default=10)
     ap.add_argument("--coatt", default="bf16", choices=["bf16", "mxfp8"],
                     help="the bank path's co-attention (mxfp8: MX-fp8 images, --dtype bf16 only)")
+    ap.add_argument("--fold-bn", action="store_true",
+                    help="the bank path with eval-mode BN folded into the conv GEMMs (model.set_bn_fold; "
+                         "--dtype bf16 / fp32); its outputs are also held against the default bank's")
     a = ap.parse_args()
+    if a.fold_bn and a.dtype == "fp8":
+        ap.error("--fold-bn runs the bf16 / fp32 encoders")
     if a.coatt == "mxfp8" and a.dtype == "fp32":
         ap.error("--coatt mxfp8 needs --dtype bf16 or fp8")
     return a
@@ -135,7 +140,20 @@ def main():
         static = m.set_fp8_static(calibrate(m, rgbs, deps, a.encode_chunk)).fp8_static
         m.set_fp8_static(None)
 
+    # --fold-bn: the tables are built once, here; the bank path switches the built state on around
+    # its calls, the per-target path and the default reference bank run with it off
+    fold = None
+    if a.fold_bn:
+        fold = m.set_bn_fold().bn_fold
+        m.set_bn_fold(False)
+
     def with_static(fn):
+        if fold is not None:
+            m.set_bn_fold(fold)
+            try:
+                return fn()
+            finally:
+                m.set_bn_fold(False)
         if static is None:
             return fn()
         m.set_fp8_static(static)
@@ -230,12 +248,20 @@ def main():
         extra["fp8_vs_bf16_bank"] = {"mask_agreement": float(((fm > 0.5) == (ref > 0.5)).double().mean()),
                                      "mean_abs_diff": float((fm - ref).abs().mean()),
                                      "max_abs_diff": float((fm - ref).abs().max())}
+    if a.fold_bn:   # the folded bank against the default bank (same co-attention setting)
+        ref = segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk, pair_chunk=a.pair_chunk,
+                               coatt=a.coatt).double().cpu()
+        fm = out_b.double().cpu()
+        extra["fold_vs_default_bank"] = {"mask_agreement": float(((fm > 0.5) == (ref > 0.5)).double().mean()),
+                                         "mean_abs_diff": float((fm - ref).abs().mean()),
+                                         "max_abs_diff": float((fm - ref).abs().max())}
     fa, fb = out_a.double().cpu(), out_b.double().cpu()
     stat = lambda v: {"mean": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v)),
                       "spread": float((np.max(v) - np.min(v)) / np.mean(v))}
     ma, mb = float(np.mean(ta)), float(np.mean(tb))
     res = {
         "tool": "seq_infer_bench", "frames": T, "nref": N, "size": H, "dtype": a.dtype, "coatt": a.coatt,
+        "fold_bn": bool(a.fold_bn),
         "seed": a.seed, "rounds": a.rounds, "warmup": max(1, a.warmup), "encode_chunk": a.encode_chunk,
         "pair_chunk": a.pair_chunk, "device": torch.cuda.get_device_name(0),
         "per_target": {"frames_per_s": T / (ma * 1e-3), "ms_per_sequence": stat(ta),
