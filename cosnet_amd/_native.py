@@ -21,6 +21,8 @@ HEADER = os.path.join(_HERE, "..", "include", "cosnet_hip.h")
 # inference extensions: launches that replace a pair of reference calls (conv2d + eval BatchNorm2d);
 # a table of their own, so the core header's entry points stay the set its tests pin
 HEADER_INFER = os.path.join(_HERE, "..", "include", "cosnet_hip_infer.h")
+# the same pairs on static-scale fp8 operands: again a table of its own, for the same reason
+HEADER_INFER_FP8 = os.path.join(_HERE, "..", "include", "cosnet_hip_infer_fp8.h")
 
 
 class NativeError(RuntimeError):
@@ -58,6 +60,7 @@ def signatures(header_text):
 
 _sigs = None
 _ext_sigs = None
+_fp8_ext_sigs = None
 
 
 def _signatures():
@@ -76,9 +79,18 @@ def _extension_signatures():
     return _ext_sigs
 
 
+def _fp8_extension_signatures():
+    global _fp8_ext_sigs
+    if _fp8_ext_sigs is None:
+        with open(HEADER_INFER_FP8) as fh:
+            _fp8_ext_sigs = signatures(fh.read())
+    return _fp8_ext_sigs
+
+
 def _signature(name):
     """The prototype of one entry point, from whichever header declares it."""
-    return _signatures().get(name) or _extension_signatures()[name]
+    return (_signatures().get(name) or _extension_signatures().get(name)
+            or _fp8_extension_signatures()[name])
 
 
 _lib = None
@@ -92,7 +104,8 @@ def load():
     if not os.path.exists(LIB_PATH):
         raise NativeError("libcosnet_hip.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args, _) in list(_signatures().items()) + list(_extension_signatures().items()):
+    for name, (res, args, _) in (list(_signatures().items()) + list(_extension_signatures().items())
+                                   + list(_fp8_extension_signatures().items())):
         # an A/B build of an older tree (COSNET_HIP_LIB) may lack the newest entry points; the
         # in-tree product library must export every one
         if os.environ.get("COSNET_HIP_LIB") and not hasattr(lib, name):
@@ -106,7 +119,7 @@ def load():
 
 HASHED_SOURCES = ["gemm.hip", "gemm_ws.hip", "conv.hip", "bn.hip", "ew.hip", "coatt.hip", "coatt_fused.hip",
                   "coatt_q48.hip", "coatt_flash.hip", "coatt_f8.hip", "fp8.hip", "frames.hip", "eval.hip",
-                  "common.h", "gemm.h", "gemm_dev.h", "coatt_fused.h", "../../include/cosnet_hip.h",
+                  "../../include/cosnet_hip_infer_fp8.h", "common.h", "gemm.h", "gemm_dev.h", "coatt_fused.h", "../../include/cosnet_hip.h",
                   "../../include/cosnet_hip_infer.h"]   # csrc/Makefile HASHED, same order
 
 
@@ -138,6 +151,11 @@ def exported_symbols():
 def extension_symbols():
     """The entry points of include/cosnet_hip_infer.h (exported_symbols() stays the core header's)."""
     return sorted(_extension_signatures())
+
+
+def fp8_extension_symbols():
+    """The entry points of include/cosnet_hip_infer_fp8.h."""
+    return sorted(_fp8_extension_signatures())
 
 
 _ERR = {-1: "shape", -2: "alignment", -3: "unsupported", -4: "hip runtime"}

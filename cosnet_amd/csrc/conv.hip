@@ -8,6 +8,7 @@
 #include "gemm.h"
 #include "../../include/cosnet_hip.h"
 #include "../../include/cosnet_hip_infer.h"
+#include "../../include/cosnet_hip_infer_fp8.h"
 
 static GemmArgs gemm_defaults() {
   GemmArgs a = {};
@@ -331,6 +332,43 @@ extern "C" int cn_conv_fwd_fp8(const void* x8, long long ldx, int N, int H, int 
   if (rc) return rc;
   a.scale_a = x_state;   // state[0] = dequantisation scale
   a.scale_b = w_state;
+  return cn_gemm_dispatch(a, DT_FP8, 0, la, L_KC_DENSE, 1, st);
+}
+
+// cn_conv_fwd_fp8 with the eval-mode BN behind it in the GEMM epilogue (gemm.h st_mode 4 on e4m3
+// operands): y (bf16) and / or y8, the e4m3 image of the same fp32 values under a frozen state.
+// No split-K route: the fp8 dispatcher has none.
+extern "C" int cn_conv_fwd_fp8_affine(const void* x8, long long ldx, int N, int H, int W, int Cin,
+                                      const void* w8, int Cout, int KH, int KW, int stride, int pad,
+                                      int dil, const float* bias, const float* x_state,
+                                      const float* w_state, const float* scale, const float* shift,
+                                      const void* res, long long ldr, int act, const float* prelu,
+                                      void* y, long long ldy, void* y8, long long ldy8,
+                                      const float* out_state, int OH, int OW, hipStream_t st) {
+  if (!fp8_operands_ok(Cin, ldx, x8, w8)) return CN_ERR_ALIGN;
+  if (!scale || !shift) return CN_ERR_SHAPE;
+  if (misaligned(scale) || misaligned(shift)) return CN_ERR_ALIGN;
+  if (!y && !y8) return CN_ERR_SHAPE;
+  if (y8 && !out_state) return CN_ERR_SHAPE;
+  if (y8 && (Cout % 8 || ldy8 % 8 || (uintptr_t)y8 % 8)) return CN_ERR_ALIGN;
+  if (act < 0 || act > 2 || (act == 2 && !prelu)) return CN_ERR_UNSUPPORTED;
+  GemmArgs a;
+  int la;
+  int rc = conv_fwd_args(DT_BF16, x8, ldx, N, H, W, Cin, w8, Cout, KH, KW, stride, pad, dil, bias, y,
+                         ldy, OH, OW, a, la);
+  if (rc) return rc;
+  a.scale_a = x_state;
+  a.scale_b = w_state;
+  a.st_mode = 4;
+  a.br_gamma = scale;
+  a.br_beta = shift;
+  a.br_x = res;
+  a.br_ldx = ldr;
+  a.act = act;
+  a.prelu = prelu;
+  a.c8 = (unsigned char*)y8;
+  a.ldc8 = ldy8;
+  a.q_state = out_state;
   return cn_gemm_dispatch(a, DT_FP8, 0, la, L_KC_DENSE, 1, st);
 }
 

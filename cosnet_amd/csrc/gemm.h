@@ -70,7 +70,10 @@ struct GemmArgs {
   //  st_mode 4: eval-mode BN folded into a forward conv (cn_conv_fwd_affine; no statistics, no
   //             grouped launch): C = act(fma(acc + bias, br_gamma[n], br_beta[n]) + br_x[m][n]),
   //             br_gamma / br_beta = the folded scale / shift, br_x / br_ldx = the residual rows
-  //             (C's type, nullable), act / prelu below.
+  //             (C's type, nullable), act / prelu below.  With e4m3 operands (bf16 C;
+  //             cn_conv_fwd_fp8_affine) the same fp32 value t is also written as its saturating
+  //             e4m3 image under a frozen state, c8 = e4m3(clamp(t * q_state[1], +-448)) -- of t
+  //             itself, not of the stored bf16 -- and either of C / c8 may be null.
   int st_mode;
   float* st_ws;
   long long st_plane;
@@ -83,6 +86,10 @@ struct GemmArgs {
                                // set by cn_gemm_dispatch
   int act;                     // st_mode 4: 0 none, 1 ReLU, 2 PReLU with the slope prelu[0]
   const float* prelu;
+  // st_mode 4 with e4m3 operands: the e4m3 output image [M][N] (nullable), its row stride in
+  // bytes, and the frozen state of the output tensor (q_state[1] = 1 / scale; only read)
+  unsigned char* c8; long long ldc8;
+  const float* q_state;
 };
 
 int cn_gemm_dispatch(const GemmArgs& a, int dtype, int c_f32, int la, int lb, int batch, hipStream_t st);

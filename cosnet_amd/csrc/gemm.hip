@@ -336,6 +336,17 @@ __device__ __forceinline__ float read_frag_f32_mc(const char* lds, int rowbase, 
   return *(const float*)(lds + k * (ROWS * 4) + col * 4);
 }
 
+// Saturating e4m3 bytes of four fp32 values (bn.hip pack4_fp8_bn: the conversion cn_bn_apply_q8
+// writes its image with)
+__device__ __forceinline__ unsigned pack4_e4m3_sat(float a, float b, float c, float d) {
+  a = fminf(fmaxf(a, -448.f), 448.f);
+  b = fminf(fmaxf(b, -448.f), 448.f);
+  c = fminf(fmaxf(c, -448.f), 448.f);
+  d = fminf(fmaxf(d, -448.f), 448.f);
+  unsigned w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  return __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+}
+
 template <class CT> __device__ __forceinline__ void store_c(CT* c, float v, int mode);
 template <> __device__ __forceinline__ void store_c<float>(float* c, float v, int mode) {
   if (mode == 1) atomicAdd(c, v);
@@ -393,7 +404,7 @@ __device__ __forceinline__ void wait_tiles(int n) {
 // ring refills in the first phase instead, and retires the third phase's reads before its
 // barrier).
 template <class T, class CT, int BM, int BN, int WM, int WN, int S, int LA, int LB, int EPI = 0, int PP = 0>
-__global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 128 * 128 && S == 2) ? 4 : 1) void gemm_kernel(GemmArgs p) {
+__global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T) == 1 && EPI == 4)) && BM * BN <= 128 * 128 && S == 2) ? 4 : 1) void gemm_kernel(GemmArgs p) {
   constexpr int NT = WM * WN * 64;
   constexpr int VEC = VecOf<T>::N;
   constexpr int BK = 8 * VEC;
@@ -526,14 +537,19 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
                                               // would otherwise cost every plain GEMM occupancy)
   constexpr bool PFC = EPI == 3;
   constexpr bool AFF = EPI == 4;              // eval-mode BN fold (st_mode 4, gemm.h)
+  constexpr bool AFF8 = AFF && sizeof(T) == 1;   // ... on e4m3 operands: C nullable, e4m3 image c8
+  static_assert(!AFF8 || sizeof(CT) == 2, "EPI 4 on fp8 operands: bf16 C");
   constexpr int PQ = (int)sizeof(CT) / 2;     // 16-B chunks per 8 elements of C
   static_assert(!PFC || sizeof(CT) == 2, "EPI 3: bf16 C");
   const int c0t = (tid % GPR) * 8;            // this thread's columns within the tile (fixed)
-  CT* Cb = (p.ngroup ? (CT*)p.grp.C[batch] : (CT*)p.C + (long long)batch * p.c_bs) +
-           (p.c_mode == 3 ? (long long)split * p.slab : 0);
+  CT* Cb;
+  if constexpr (AFF8) Cb = (CT*)p.C;          // batch 1, no group, c_mode 0; may be null
+  else Cb = (p.ngroup ? (CT*)p.grp.C[batch] : (CT*)p.C + (long long)batch * p.c_bs) +
+            (p.c_mode == 3 ? (long long)split * p.slab : 0);
   u32x4 xnx[(smode == 2 || PFC || AFF) ? IT * PQ : 1];   // the next staging pass's rows
   // write-through C stores (p.wt): the block's rows from its first one, 32-bit offsets
-  const __amdgpu_buffer_rsrc_t crs = buf_rsrc(Cb + (long long)m0 * p.ldc);
+  // (AFF8 stores through pointers only: no descriptor is formed from a C that may be null)
+  const __amdgpu_buffer_rsrc_t crs = buf_rsrc(AFF8 ? (CT*)nullptr : Cb + (long long)m0 * p.ldc);
   auto epi_fetch = [&](int pass) {
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
@@ -562,7 +578,11 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
   // (tiles without the 128-VGPR occupancy bound of the 2-stage BN-epilogue kernels and below
   // 256 x 256, whose accumulators fill the register file; tools/kernel_resources.py checks)
   // (AFF: every tile but the 256 x 256 ping-pong tile on the per-thread-pointer gather, which spills)
-  constexpr bool EARLY = PFC || (AFF && !(LA == L_KC_CONV_G && BM * BN == 256 * 256 && PP == 1)) ||
+  // (AFF8: the 2-stage 128 x 128 tile on the two conv gathers keeps the plain fp8 kernel's two
+  // blocks per CU only within 128 VGPRs, where the prefetch and the scale / shift values live
+  // across the K loop spill 2-3 registers: those two fetch at the start of the pass)
+  constexpr bool EARLY = PFC || (AFF && !(LA == L_KC_CONV_G && BM * BN == 256 * 256 && PP == 1) &&
+                                 !(AFF8 && LA != L_KC_DENSE && BM * BN == 128 * 128 && S == 2)) ||
                          (smode == 2 && S >= 3 && BM * BN <= 128 * 128);
   float bk1[8], bsf[8], bmu[8];
   float fsc[8], fsh[8];   // AFF: this thread's eight folded scale / shift values
@@ -587,6 +607,8 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
       bsf[e] = b - bmu[e] * bk1[e];     // recomputed ReLU mask has exactly the forward's sign
     }
   };
+  float qinv = 0.f;       // AFF8: the output state's inverse scale
+  if constexpr (AFF8) { if (p.c8) qinv = p.q_state[1]; }
   if constexpr (EARLY) {
     if constexpr (smode == 2) epi_affine();
     if constexpr (AFF) epi_fold();
@@ -886,7 +908,7 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
       float v[8];
       *(f32x4*)&v[0] = *(const f32x4*)&cs[rr * LDC + c0];
       *(f32x4*)&v[4] = *(const f32x4*)&cs[rr * LDC + c0 + 4];
-      CT* dst = Cb + drow * p.ldc + col;
+      CT* dst = (AFF8 && !Cb) ? (CT*)nullptr : Cb + drow * p.ldc + col;
       const bool full = col + 8 <= p.N && ((uintptr_t)dst % 16 == 0);
       if (bias) {
 #pragma unroll
@@ -913,6 +935,26 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && sizeof(T) == 2 && BM * BN <= 
           else if (p.act == 2) t = t > 0.f ? t : slope * t;
           v[e] = t;
         }
+      }
+      if constexpr (AFF8) {   // bf16 C and / or the e4m3 image of the same fp32 values
+        if (p.c8 && col + 8 <= p.N) {
+          u32x2 o;
+          o.x = pack4_e4m3_sat(v[0] * qinv, v[1] * qinv, v[2] * qinv, v[3] * qinv);
+          o.y = pack4_e4m3_sat(v[4] * qinv, v[5] * qinv, v[6] * qinv, v[7] * qinv);
+          *(u32x2*)(p.c8 + (long long)row * p.ldc8 + col) = o;
+        }
+        if (dst) {
+          if (full) {
+            const u32x4 pk = Chunk<bf16>::pack(v);
+            if (p.wt == 4) __builtin_nontemporal_store(pk, (u32x4*)dst);
+            else *(u32x4*)dst = pk;
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (col + e < p.N) dst[e] = (bf16)v[e];
+          }
+        }
+        continue;
       }
       if (cmode == 1) {
 #pragma unroll
@@ -1241,6 +1283,12 @@ static int launch_f8(const GemmArgs& a, int batch, hipStream_t st) {
       if (c == 13) return launch_c<T8, CT, 13, LA, L_KC_DENSE, 1>(a, batch, st);
       return launch_c<T8, CT, 11, LA, L_KC_DENSE, 1>(a, batch, st);
     }
+    // fp8 conv forward with the eval-mode BN fold (cn_conv_fwd_fp8_affine; the bf16 path's EPI 4)
+    if (a.st_mode == 4) {
+      if (c == 12) return launch_c<T8, CT, 12, LA, L_KC_DENSE, 4>(a, batch, st);
+      if (c == 13) return launch_c<T8, CT, 13, LA, L_KC_DENSE, 4>(a, batch, st);
+      return launch_c<T8, CT, 11, LA, L_KC_DENSE, 4>(a, batch, st);
+    }
   }
   if (a.st_mode) return CN_ERR_UNSUPPORTED;
   if (c == 12) return launch_c<T8, CT, 12, LA, L_KC_DENSE>(a, batch, st);
@@ -1314,7 +1362,16 @@ int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb,
   }
   if (dtype == DT_FP8) {
     if (lb != L_KC_DENSE || a.nsplit != 1) return CN_ERR_UNSUPPORTED;
-    if (a.st_mode && (a.st_mode != 1 || batch != 1 || a.row_map || a.c_mode || c_f32)) return CN_ERR_UNSUPPORTED;
+    if (a.st_mode && ((a.st_mode != 1 && a.st_mode != 4) || batch != 1 || a.row_map || a.c_mode || c_f32))
+      return CN_ERR_UNSUPPORTED;
+    if (a.st_mode == 4) {   // the eval-mode BN fold: bf16 C and / or the e4m3 image
+      if (a.ngroup || !a.br_gamma || !a.br_beta || a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu) ||
+          (!a.C && !a.c8) || (a.c8 && !a.q_state))
+        return CN_ERR_UNSUPPORTED;
+      // a forced configuration that has no folded epilogue is refused, not replaced
+      const int fc = g_force_cfg >= 0 && g_force_cfg < kNumCfg ? g_force_cfg : a.cfg;
+      if (fc >= 0 && fc < kNumCfg && fc != 11 && fc != 12 && fc != 13) return CN_ERR_UNSUPPORTED;
+    }
     if (la == L_KC_DENSE) return c_f32 ? launch_f8<float, L_KC_DENSE>(a, batch, st) : launch_f8<bf16, L_KC_DENSE>(a, batch, st);
     if (la == L_KC_CONV) return c_f32 ? launch_f8<float, L_KC_CONV>(a, batch, st) : launch_f8<bf16, L_KC_CONV>(a, batch, st);
     if (la == L_KC_CONV_G) return c_f32 ? launch_f8<float, L_KC_CONV_G>(a, batch, st) : launch_f8<bf16, L_KC_CONV_G>(a, batch, st);

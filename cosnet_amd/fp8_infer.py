@@ -25,6 +25,13 @@ Here the scales are calibrated once and frozen:
 One state per tensor: a block's input, read by its conv1 and its downsample conv, has one
 ("<block>.x"); so have its y1 and y2, the ASPP's input ("aspp.x") and the whole concat
 ("aspp.cat").
+
+set_fp8_static(calib, fold_bn=True) also folds every eval-mode BatchNorm into its conv's GEMM:
+bottleneck_static_folded / aspp_static_folded run each conv + BN pair as ONE launch,
+cn_conv_fwd_fp8_affine (gemm.hip EPI 4 on e4m3 operands), whose epilogue applies the BN's
+(scale, shift) table (bn_fold.FoldTables), the residual add and the activation and writes the
+bf16 result and / or its e4m3 image under the consumer's frozen state.  No raw conv output is
+written and cn_bn_eval_params / cn_bn_apply_q8 do not run.
 """
 import json
 import weakref
@@ -176,9 +183,11 @@ def calibrate(model, rgbs, depths, encode_chunk=8, margin=1.0):
 
 # ---- the frozen context ------------------------------------------------------------------------
 class EncoderStatic:
-    """One encoder's frozen state table [n][4] = (scale, 1/scale, 0, 448) and its e4m3 weights."""
+    """One encoder's frozen state table [n][4] = (scale, 1/scale, 0, 448) and its e4m3 weights;
+    with fold_bn, also the (scale, shift) table of every BatchNorm2d of the encoder
+    (bn_fold.FoldTables: its staleness rule, cn_bn_fold_table)."""
 
-    def __init__(self, enc, amax, margin, device):
+    def __init__(self, enc, amax, margin, device, fold_bn=False):
         self.names = state_names(enc)
         self.slot = {n: i for i, n in enumerate(self.names)}
         self.paths = _paths(enc)
@@ -193,6 +202,10 @@ class EncoderStatic:
                 raise ValueError("static fp8: a conv of %d input channels cannot take fp8 operands"
                                  % w.shape[1])
             self.weights.get(w)   # quantised now: nothing is calibrated on first use
+        self.fold = None
+        if fold_bn:
+            from .bn_fold import FoldTables
+            self.fold = FoldTables(enc)
 
     def st(self, name):
         return self.states[self.slot[name]]
@@ -202,17 +215,26 @@ class EncoderStatic:
 
 
 class Fp8Static:
-    """A model's static fp8 mode (model.set_fp8_static): one EncoderStatic per encoder."""
+    """A model's static fp8 mode (model.set_fp8_static): one EncoderStatic per encoder.  With
+    fold_bn the state also owns the fold tables of both encoders and of the two reduce convs' BNs
+    of the a-side head (`head`; None otherwise), and the encoders run the folded walk."""
 
-    def __init__(self, model, calib):
+    def __init__(self, model, calib, fold_bn=False):
         calib.check_model(model)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("set_fp8_static: the model must be on the GPU")
         self.calibration = calib
         self.model = weakref.ref(model)
-        self.encoders = {k: EncoderStatic(getattr(model, k), calib.amax[k], calib.margin, dev)
+        self.fold_bn = bool(fold_bn)
+        if self.fold_bn and model.training:
+            raise RuntimeError("set_fp8_static: the BN fold uses running statistics (eval mode)")
+        self.encoders = {k: EncoderStatic(getattr(model, k), calib.amax[k], calib.margin, dev, self.fold_bn)
                          for k in ENCODERS}
+        self.head = None
+        if self.fold_bn:
+            from .bn_fold import FoldTables
+            self.head = FoldTables(model, modules=[("bn_A", model.bn_A), ("depth_bn", model.depth_bn)])
 
 
 def _eval_stats(c, bn):
@@ -273,17 +295,83 @@ def aspp_static(mod, x, x8, geo, S):
     return ops.bn_apply(cb, _eval_stats(cb, mod.bn), mod.bn, act=2, prelu=mod.prelu.weight)
 
 
+# ---- the same walk with every conv + eval BN pair as one launch (set_fp8_static(fold_bn=True)) ----
+def _conv8_folded(S, x8, n, h, w, conv, bn, cout, k, stride, pad, dil, x_state, **kw):
+    """One fp8 conv + eval BN pair: cn_conv_fwd_fp8_affine on the conv's frozen e4m3 weight and
+    the BN's fold table."""
+    w8, ws = S.w8(conv.weight)
+    sc, sf = S.fold.get(bn)
+    return ops.conv_fwd_fp8_affine(x8, n, h, w, w8, cout, k, stride, pad, dil, x_state, ws, sc, sf, **kw)
+
+
+def bottleneck_static_folded(blk, x, x8, geo, S, out_state):
+    """bottleneck_static with the BNs in the conv GEMMs' epilogues, three launches (four with a
+    downsample): conv1 and conv2 write y1 / y2 as e4m3 only; the downsample conv writes
+    rd = affine(cd) as bf16 with no activation; conv3 takes rd (or x) as its residual and writes
+    y (bf16) and its e4m3 image under out_state.  No raw conv output exists."""
+    n, h, w = geo
+    s, d = blk.stride, blk.dilation
+    planes = blk.conv1.weight.shape[0]
+    name = S.paths[id(blk)]
+    sx, s1, s2 = S.st(name + ".x"), S.st(name + ".y1"), S.st(name + ".y2")
+    _, y18, oh, ow = _conv8_folded(S, x8, n, h, w, blk.conv1, blk.bn1, planes, 1, s, 0, 1, sx, act=1,
+                                   out_state=s1, want_y=False)
+    _, y28, _, _ = _conv8_folded(S, y18, n, oh, ow, blk.conv2, blk.bn2, planes, 3, 1, d, d, s1, act=1,
+                                 out_state=s2, want_y=False)
+    res = x
+    if blk.downsample is not None:
+        res, _, _, _ = _conv8_folded(S, x8, n, h, w, blk.downsample[0], blk.downsample[1], 4 * planes,
+                                     1, s, 0, 1, sx, act=0)
+    y, y8, _, _ = _conv8_folded(S, y28, n, oh, ow, blk.conv3, blk.bn3, 4 * planes, 1, 1, 0, 1, s2, act=1,
+                                res=res, out_state=out_state)
+    return y, y8, (n, oh, ow)
+
+
+def aspp_static_folded(mod, x, x8, geo, S):
+    """aspp_static with the BNs folded: the pooled 1x1 conv is bf16 (cn_conv_fwd_affine), the four
+    branches write their e4m3 slices of the concat in place, the bottleneck conv writes bf16 with
+    the PReLU applied."""
+    n, h, w = geo
+    hw = h * w
+    P = n * hw
+    dt = x.dtype
+    name = S.paths[id(mod)]
+    sx, sc = S.st(name + ".x"), S.st(name + ".cat")
+    pool = torch.empty((n, 2048), dtype=dt, device=x.device)
+    ops.avgpool(x, n, hw, 1.0 / hw, pool)
+    wcf, _ = WCACHE.get(mod.conv.weight, dt)
+    psc, psf = S.fold.get(mod.bn_x)
+    yp, _, _ = ops.conv_fwd_affine(pool, n, 1, 1, wcf, 512, 1, 1, 0, 1, psc, psf, act=1, bias=mod.conv.bias)
+    cat8 = torch.empty((P, 2560), dtype=torch.uint8, device=x.device)
+    ops.bcast_rows_u8(ops.fp8_quant_static(yp, sc), n, hw, cat8[:, :512])
+    for bi, (cm, bnm, k, dd) in enumerate(E.aspp_branches(mod)):
+        _conv8_folded(S, x8, n, h, w, cm, bnm, 512, k, 1, dd, max(dd, 1), sx, act=1, bias=cm.bias,
+                      out8=cat8[:, 512 * (bi + 1):512 * (bi + 2)], out_state=sc, want_y=False)
+    out, _, _, _ = _conv8_folded(S, cat8, n, h, w, mod.bottleneck, mod.bn, 256, 3, 1, 1, 1, sc, act=2,
+                                 prelu=mod.prelu.weight, bias=mod.bottleneck.bias)
+    return out
+
+
 def encode_frames_static(enc, imgs):
     """imgs [n,C,H,W] fp32 NCHW on the GPU -> (feats [n*h*w][256] bf16, (n, h, w)): one encoder
-    on frozen fp8 scales (model.set_fp8_static).  Eval mode under no_grad."""
+    on frozen fp8 scales (model.set_fp8_static).  Eval mode under no_grad.  A static state that
+    carries fold tables (set_fp8_static(fold_bn=True)) takes the folded block functions: the same
+    walk order, one launch per conv + BN pair."""
     S = getattr(enc, "_cn_fp8_static", None)
     if S is None:
         raise RuntimeError("encode_frames_static: no static fp8 scales (model.set_fp8_static)")
     if enc.training or torch.is_grad_enabled():
         raise RuntimeError("static fp8 is an inference path: eval mode under torch.no_grad()")
     dt = torch.bfloat16
-    with E.no_fp8():   # the stem is not an fp8 conv: as the bf16 path runs it
-        x, geo = E.stem_fwd(enc.backbone, (imgs,), 1, dt, None)
+    folded = S.fold is not None
+    bottleneck, aspp = ((bottleneck_static_folded, aspp_static_folded) if folded
+                        else (bottleneck_static, aspp_static))
+    if folded:   # the stem is bf16 either way: conv + BN as the bf16 fold runs it
+        from .bn_fold import stem_folded
+        x, geo = stem_folded(enc.backbone, imgs, dt, S.fold)
+    else:
+        with E.no_fp8():   # the stem is not an fp8 conv: as the bf16 path runs it
+            x, geo = E.stem_fwd(enc.backbone, (imgs,), 1, dt, None)
     n, h, w = geo
     fh, fw = ops.out_hw(h, w, 1, 2, 0, 1)   # layer2's stride; layers 3-4 keep the size
     if not fp8_rows_ok(n * fh * fw):
@@ -295,5 +383,5 @@ def encode_frames_static(enc, imgs):
     x8 = ops.fp8_quant_static(x, S.st(S.paths[id(blocks[0])] + ".x"))
     for i, blk in enumerate(blocks):
         nxt = S.paths[id(blocks[i + 1] if i + 1 < len(blocks) else enc.aspp)] + ".x"
-        x, x8, geo = bottleneck_static(blk, x, x8, geo, S, S.st(nxt))
-    return aspp_static(enc.aspp, x, x8, geo, S), geo
+        x, x8, geo = bottleneck(blk, x, x8, geo, S, S.st(nxt))
+    return aspp(enc.aspp, x, x8, geo, S), geo

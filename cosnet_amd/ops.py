@@ -455,6 +455,46 @@ def conv_fwd_fp8(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_state, 
     return out, g.oh, g.ow
 
 
+def _fwd8_affine_record(tag, g, has_res, has_y, has_y8):
+    """The fp8 conv with the eval-mode BN folded in: one-byte operands, a bf16 residual, and
+    whichever of the bf16 output and its e4m3 image the launch writes."""
+    fl, tg, nb = _fwd_record(tag, g, 1, 0)
+    return fl, tg, nb + g.M * g.cout * (2 * has_res + 2 * has_y + has_y8)
+
+
+def conv_fwd_fp8_affine(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_state, scale, shift,
+                        act=0, prelu=None, res=None, bias=None, out=None, out8=None, out_state=None,
+                        want_y=True):
+    """act(fma(conv(x8, w8) * sx * sw + bias, scale, shift) + res) in one launch
+    (cn_conv_fwd_fp8_affine): the static-scale fp8 conv and the eval-mode BatchNorm behind it.
+    y (bf16 [M, cout]; `out`, or allocated unless want_y is False) is one rounding of the fp32
+    value; y8 (e4m3 bytes; `out8`, or allocated) is written when out_state, the FROZEN state of the
+    output tensor, is given, and is the image of the fp32 value, not of y.  scale / shift fp32
+    [cout] from bn_fold_table; res a bf16 [M, cout] view.  -> (y or None, y8 or None, oh, ow)."""
+    cin = wf8.shape[1] // (k * k)
+    oh, ow = out_hw(h, w, k, stride, pad, dil)
+    g = _Conv(n, h, w, cin, oh, ow, cout, k, n * oh * ow, k * k * cin)
+    if out is None and want_y:
+        out = torch.empty((g.M, cout), dtype=torch.bfloat16, device=x8.device)
+    if out8 is None and out_state is not None:
+        out8 = torch.empty((g.M, cout), dtype=torch.uint8, device=x8.device)
+    if out is None and out8 is None:
+        raise ValueError("conv_fwd_fp8_affine: nothing to write (want_y=False without out_state)")
+    if out8 is not None and out_state is None:
+        raise ValueError("conv_fwd_fp8_affine: the e4m3 image needs the output's frozen state")
+    if res is not None and (res.dtype != torch.bfloat16 or tuple(res.shape) != (g.M, cout)):
+        raise ValueError("conv_fwd_fp8_affine: res must be a bf16 [%d, %d] view" % (g.M, cout))
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != cout or t.stride(0) != 1:
+            raise ValueError("conv_fwd_fp8_affine: scale / shift are fp32 [%d] arrays" % cout)
+    with _profiled(_fwd8_affine_record, "fwd8_affine", g, res is not None, out is not None, out8 is not None):
+        nv.call("cn_conv_fwd_fp8_affine", x8.data_ptr(), ld(x8), n, h, w, cin, wf8.data_ptr(), cout, k, k,
+                stride, pad, dil, nv.ptr(bias), x_state.data_ptr(), w_state.data_ptr(), scale.data_ptr(),
+                shift.data_ptr(), *_mat(res, 0), int(act), nv.ptr(prelu), *_mat(out, 0), *_mat(out8, 0),
+                nv.ptr(out_state), oh, ow, nv.stream())
+    return out, out8, oh, ow
+
+
 def conv_fwd_bn_grouped(x, n, h, w, wfs, cout, k, dils, bns, nseg=1, biases=None):
     """The ASPP's atrous branches as ONE grouped launch (cn_conv_fwd_bn_grouped): for each g,
     y_g = conv(x, wfs[g], dilation dils[g], padding dils[g]) (+ biases[g]) and the BN batch

@@ -159,13 +159,18 @@ class RGBDSegmentation_RAA(nn.Module):
         self._fp8_depth = Fp8Context() if on else None
         return self
 
-    def set_fp8_static(self, calibration):
+    def set_fp8_static(self, calibration, fold_bn=False):
         """Static-scale fp8 encoders for whole-sequence inference (cosnet_amd/fp8_infer.py): the
         frozen state tables of an Fp8Calibration are built on the device and every eligible conv
         weight is quantised now, so nothing is calibrated on first use.  FeatureBank.encode /
         segment_sequence then run both encoders on e4m3 conv GEMMs whose scales no launch writes.
         None switches it off; the built state (model.fp8_static) given back switches it on again
-        without rebuilding.  Needs the bf16 compute dtype; exclusive with set_fp8(True)."""
+        without rebuilding.  Needs the bf16 compute dtype; exclusive with set_fp8(True).
+        fold_bn=True (eval mode) also folds every eval-mode BatchNorm of both encoders into its
+        conv's GEMM epilogue (cn_conv_fwd_fp8_affine: one launch per conv + BN pair) and the two
+        reduce convs' BNs of head_a_indexed (cn_conv_fwd_affine); the fold tables belong to the
+        static state, model.bn_fold stays None, and a built state handed back keeps the fold state
+        it was built with."""
         if calibration is None:
             self.fp8_static = None
             for enc in (self.encoder, self.depth_encoder):
@@ -183,7 +188,7 @@ class RGBDSegmentation_RAA(nn.Module):
             if st.model() is not self:
                 raise ValueError("set_fp8_static: the static fp8 state was built for another model")
         else:
-            st = Fp8Static(self, calibration)
+            st = Fp8Static(self, calibration, fold_bn)
         self.fp8_static = st
         self.encoder._cn_fp8_static = st.encoders["encoder"]
         self.depth_encoder._cn_fp8_static = st.encoders["depth_encoder"]
@@ -342,6 +347,8 @@ class RGBDSegmentation_RAA(nn.Module):
         if getattr(self, "fp8", None) is not None:
             raise RuntimeError("head_a_indexed: fp8 banks are not supported (set_fp8(False))")
         fold = getattr(self, "bn_fold", None)   # set_bn_fold: the reduce conv and its BN in one launch
+        if fold is None and getattr(getattr(self, "fp8_static", None), "head", None) is not None:
+            fold = self.fp8_static   # set_fp8_static(fold_bn=True): the same bf16 launch, its own tables
         self._set_dtype()
         t, h, w = bank.geo
         hw = h * w

@@ -63,6 +63,10 @@ def get_arguments(argv=None):
     p.add_argument("--fold-bn", action="store_true",
                    help="--feature-bank (bf16 / fp32): every conv + eval-mode BatchNorm pair of the encoders and "
                         "of the head's reduce convs as one launch (cosnet_amd/bn_fold.py)")
+    p.add_argument("--fp8-fold-bn", action="store_true",
+                   help="--feature-bank --dtype fp8: every fp8 conv + eval-mode BatchNorm pair of the encoders as "
+                        "one launch (cn_conv_fwd_fp8_affine) and the head's reduce convs folded "
+                        "(model.set_fp8_static(calibration, fold_bn=True))")
     p.add_argument("--fp8-calibration", default=None, metavar="FILE",
                    help="--dtype fp8: the calibration (JSON).  Loaded if the file exists; otherwise made "
                         "before evaluation from the first --fp8-calibration-frames test frames and written there")
@@ -78,6 +82,8 @@ def get_arguments(argv=None):
         p.error("--fold-bn needs --feature-bank")
     if args.fold_bn and args.dtype == "fp8":
         p.error("--fold-bn runs the bf16 / fp32 encoders (not --dtype fp8)")
+    if args.fp8_fold_bn and not (args.feature_bank and args.dtype == "fp8"):
+        p.error("--fp8-fold-bn needs --feature-bank --dtype fp8")
     if args.dtype == "fp8" and args.fp8_calibration_frames < 1:
         p.error("--fp8-calibration-frames must be at least 1")
     if args.dtype != "fp8" and args.fp8_calibration:
@@ -182,7 +188,7 @@ def main(argv=None):
             calib = calibrate(model, *load_frames(args.fp8_calibration_frames))
             if path:
                 calib.save(path)
-        model.set_fp8_static(calib)
+        model.set_fp8_static(calib, fold_bn=args.fp8_fold_bn)
 
     db = None
     if args.dataset == "sbmrgbd":

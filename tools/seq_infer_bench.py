@@ -61,9 +61,14 @@ def parse():
     ap.add_argument("--fold-bn", action="store_true",
                     help="the bank path with eval-mode BN folded into the conv GEMMs (model.set_bn_fold; "
                          "--dtype bf16 / fp32); its outputs are also held against the default bank's")
+    ap.add_argument("--fp8-fold-bn", action="store_true",
+                    help="--dtype fp8: eval-mode BN folded into the static-scale fp8 conv GEMMs "
+                         "(model.set_fp8_static(calibration, fold_bn=True))")
     a = ap.parse_args()
     if a.fold_bn and a.dtype == "fp8":
         ap.error("--fold-bn runs the bf16 / fp32 encoders")
+    if a.fp8_fold_bn and a.dtype != "fp8":
+        ap.error("--fp8-fold-bn needs --dtype fp8")
     if a.coatt == "mxfp8" and a.dtype == "fp32":
         ap.error("--coatt mxfp8 needs --dtype bf16 or fp8")
     return a
@@ -137,7 +142,7 @@ def main():
     static = None
     if a.dtype == "fp8":
         from cosnet_amd.fp8_infer import calibrate
-        static = m.set_fp8_static(calibrate(m, rgbs, deps, a.encode_chunk)).fp8_static
+        static = m.set_fp8_static(calibrate(m, rgbs, deps, a.encode_chunk), fold_bn=a.fp8_fold_bn).fp8_static
         m.set_fp8_static(None)
 
     # --fold-bn: the tables are built once, here; the bank path switches the built state on around
@@ -261,7 +266,7 @@ def main():
     ma, mb = float(np.mean(ta)), float(np.mean(tb))
     res = {
         "tool": "seq_infer_bench", "frames": T, "nref": N, "size": H, "dtype": a.dtype, "coatt": a.coatt,
-        "fold_bn": bool(a.fold_bn),
+        "fold_bn": bool(a.fold_bn), "fp8_fold_bn": bool(a.fp8_fold_bn),
         "seed": a.seed, "rounds": a.rounds, "warmup": max(1, a.warmup), "encode_chunk": a.encode_chunk,
         "pair_chunk": a.pair_chunk, "device": torch.cuda.get_device_name(0),
         "per_target": {"frames_per_s": T / (ma * 1e-3), "ms_per_sequence": stat(ta),
