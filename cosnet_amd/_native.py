@@ -23,6 +23,8 @@ HEADER = os.path.join(_HERE, "..", "include", "cosnet_hip.h")
 HEADER_INFER = os.path.join(_HERE, "..", "include", "cosnet_hip_infer.h")
 # the same pairs on static-scale fp8 operands: again a table of its own, for the same reason
 HEADER_INFER_FP8 = os.path.join(_HERE, "..", "include", "cosnet_hip_infer_fp8.h")
+# the bank head's split reduce conv (the per-frame partial and the conv that adds it): likewise
+HEADER_INFER_HEAD = os.path.join(_HERE, "..", "include", "cosnet_hip_infer_head.h")
 
 
 class NativeError(RuntimeError):
@@ -61,6 +63,7 @@ def signatures(header_text):
 _sigs = None
 _ext_sigs = None
 _fp8_ext_sigs = None
+_head_ext_sigs = None
 
 
 def _signatures():
@@ -87,10 +90,18 @@ def _fp8_extension_signatures():
     return _fp8_ext_sigs
 
 
+def _head_extension_signatures():
+    global _head_ext_sigs
+    if _head_ext_sigs is None:
+        with open(HEADER_INFER_HEAD) as fh:
+            _head_ext_sigs = signatures(fh.read())
+    return _head_ext_sigs
+
+
 def _signature(name):
     """The prototype of one entry point, from whichever header declares it."""
     return (_signatures().get(name) or _extension_signatures().get(name)
-            or _fp8_extension_signatures()[name])
+            or _fp8_extension_signatures().get(name) or _head_extension_signatures()[name])
 
 
 _lib = None
@@ -105,7 +116,8 @@ def load():
         raise NativeError("libcosnet_hip.so not built (%s); run __graft_entry__.build()" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     for name, (res, args, _) in (list(_signatures().items()) + list(_extension_signatures().items())
-                                   + list(_fp8_extension_signatures().items())):
+                                   + list(_fp8_extension_signatures().items())
+                                   + list(_head_extension_signatures().items())):
         # an A/B build of an older tree (COSNET_HIP_LIB) may lack the newest entry points; the
         # in-tree product library must export every one
         if os.environ.get("COSNET_HIP_LIB") and not hasattr(lib, name):
@@ -119,7 +131,7 @@ def load():
 
 HASHED_SOURCES = ["gemm.hip", "gemm_ws.hip", "conv.hip", "bn.hip", "ew.hip", "coatt.hip", "coatt_fused.hip",
                   "coatt_q48.hip", "coatt_flash.hip", "coatt_f8.hip", "fp8.hip", "frames.hip", "eval.hip",
-                  "../../include/cosnet_hip_infer_fp8.h", "common.h", "gemm.h", "gemm_dev.h", "coatt_fused.h", "../../include/cosnet_hip.h",
+                  "../../include/cosnet_hip_infer_fp8.h", "../../include/cosnet_hip_infer_head.h", "common.h", "gemm.h", "gemm_dev.h", "coatt_fused.h", "../../include/cosnet_hip.h",
                   "../../include/cosnet_hip_infer.h"]   # csrc/Makefile HASHED, same order
 
 
@@ -156,6 +168,11 @@ def extension_symbols():
 def fp8_extension_symbols():
     """The entry points of include/cosnet_hip_infer_fp8.h."""
     return sorted(_fp8_extension_signatures())
+
+
+def head_extension_symbols():
+    """The entry points of include/cosnet_hip_infer_head.h."""
+    return sorted(_head_extension_signatures())
 
 
 _ERR = {-1: "shape", -2: "alignment", -3: "unsupported", -4: "hip runtime"}

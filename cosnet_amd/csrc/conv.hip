@@ -9,6 +9,7 @@
 #include "../../include/cosnet_hip.h"
 #include "../../include/cosnet_hip_infer.h"
 #include "../../include/cosnet_hip_infer_fp8.h"
+#include "../../include/cosnet_hip_infer_head.h"
 
 static GemmArgs gemm_defaults() {
   GemmArgs a = {};
@@ -316,6 +317,53 @@ extern "C" int cn_conv_fwd_affine(int dtype, const void* x, long long ldx, int N
                      M, Cout, bias, scale, shift, (const bf16*)res, ldr, act, prelu, (bf16*)y, ldy);
   CN_CHECK_LAUNCH();
   return 0;
+}
+
+// ---- a conv split by input channels: the unrounded partial, and the conv that adds it --------
+// (include/cosnet_hip_infer_head.h).  The partial is the plain GEMM with an fp32 C; no split over K.
+extern "C" int cn_conv_fwd_partial(int dtype, const void* x, long long ldx, int N, int H, int W, int Cin,
+                                   const void* w, int Cout, int KH, int KW, int stride, int pad, int dil,
+                                   const float* bias, void* y, long long ldy, int OH, int OW,
+                                   hipStream_t st) {
+  if (dtype != DT_BF16 && dtype != DT_F32) return CN_ERR_UNSUPPORTED;
+  GemmArgs a;
+  int la;
+  int rc = conv_fwd_args(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, bias, y, ldy,
+                         OH, OW, a, la);
+  if (rc) return rc;
+  return cn_gemm_dispatch(a, dtype, 1, la, L_KC_DENSE, 1, st);
+}
+
+// cn_conv_fwd_affine with an fp32 addend looked up per block of add_rows output rows in front of the
+// affine (gemm.h st_mode 5).  No residual, no split over K, no weight-stationary route.
+extern "C" int cn_conv_fwd_affine_add(int dtype, const void* x, long long ldx, int N, int H, int W,
+                                      int Cin, const void* w, int Cout, int KH, int KW, int stride,
+                                      int pad, int dil, const float* bias, void* y, long long ldy,
+                                      int OH, int OW, const float* scale, const float* shift,
+                                      const float* add, long long lda, const int* add_map, int add_rows,
+                                      int act, const float* prelu, hipStream_t st) {
+  if (dtype != DT_BF16 && dtype != DT_F32) return CN_ERR_UNSUPPORTED;
+  if (!scale || !shift) return CN_ERR_SHAPE;
+  if (misaligned(scale) || misaligned(shift) || misaligned(add_map, 4)) return CN_ERR_ALIGN;
+  if (act < 0 || act > 2 || (act == 2 && !prelu)) return CN_ERR_UNSUPPORTED;
+  if (!add || add_rows <= 0 || lda < Cout) return CN_ERR_SHAPE;
+  GemmArgs a;
+  int la;
+  int rc = conv_fwd_args(dtype, x, ldx, N, H, W, Cin, w, Cout, KH, KW, stride, pad, dil, bias, y, ldy,
+                         OH, OW, a, la);
+  if (rc) return rc;
+  if (a.M % add_rows) return CN_ERR_SHAPE;
+  a.st_mode = 5;
+  a.br_gamma = scale;
+  a.br_beta = shift;
+  a.act = act;
+  a.prelu = prelu;
+  a.add = add;
+  a.add_ld = lda;
+  a.add_map = add_map;
+  a.add_rows = add_rows;
+  a.add_div = fastdiv_make(add_rows);
+  return cn_gemm_dispatch(a, dtype, dtype == DT_F32, la, L_KC_DENSE, 1, st);
 }
 
 // y (bf16) = conv2d(x8, w8) * x_scale * w_scale (+ bias): fp8 e4m3 operands (cn_fp8_quant), fp32

@@ -84,12 +84,22 @@ struct GemmArgs {
   GemmGroup grp;
   int wt;                      // C stores: 4 non-temporal, 0 plain (other: write-through, sc1);
                                // set by cn_gemm_dispatch
-  int act;                     // st_mode 4: 0 none, 1 ReLU, 2 PReLU with the slope prelu[0]
+  int act;                     // st_mode 4 / 5: 0 none, 1 ReLU, 2 PReLU with the slope prelu[0]
   const float* prelu;
   // st_mode 4 with e4m3 operands: the e4m3 output image [M][N] (nullable), its row stride in
   // bytes, and the frozen state of the output tensor (q_state[1] = 1 / scale; only read)
   unsigned char* c8; long long ldc8;
   const float* q_state;
+  // st_mode 5: st_mode 4 with an fp32 addend in front of the affine instead of the residual behind
+  //            it (cn_conv_fwd_affine_add; bf16 / fp32 operands, no grouped launch):
+  //            C = act(fma(acc + bias + add[f * add_rows + r][n], br_gamma[n], br_beta[n])) for
+  //            row m = j * add_rows + r, f = add_map ? add_map[j] : j.  add: fp32 rows add_ld floats
+  //            apart (64-bit row addressing); add_map: device int32, one entry per block of
+  //            add_rows output rows, not range-checked; add_div = fastdiv_make(add_rows).
+  const float* add; long long add_ld;
+  const int* add_map;
+  int add_rows;
+  FastDiv add_div;
 };
 
 int cn_gemm_dispatch(const GemmArgs& a, int dtype, int c_f32, int la, int lb, int batch, hipStream_t st);

@@ -533,11 +533,13 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
   constexpr int RPP = NT / GPR;          // rows per pass
   constexpr int IT = HR / RPP;           // rows per thread per pass
   static_assert(IT * RPP == HR, "epilogue rows per pass must be a multiple of the row stride");
-  constexpr int smode = (EPI == 3 || EPI == 4) ? 0 : EPI;   // BN epilogue (compile-time: its registers
+  constexpr int smode = (EPI == 3 || EPI == 4 || EPI == 5) ? 0 : EPI;   // BN epilogue (compile-time: its registers
                                               // would otherwise cost every plain GEMM occupancy)
   constexpr bool PFC = EPI == 3;
   constexpr bool AFF = EPI == 4;              // eval-mode BN fold (st_mode 4, gemm.h)
   constexpr bool AFF8 = AFF && sizeof(T) == 1;   // ... on e4m3 operands: C nullable, e4m3 image c8
+  constexpr bool ADD = EPI == 5;              // ... with an fp32 addend in front of it (st_mode 5)
+  static_assert(!ADD || sizeof(T) >= 2, "EPI 5: bf16 / fp32 operands");
   static_assert(!AFF8 || sizeof(CT) == 2, "EPI 4 on fp8 operands: bf16 C");
   constexpr int PQ = (int)sizeof(CT) / 2;     // 16-B chunks per 8 elements of C
   static_assert(!PFC || sizeof(CT) == 2, "EPI 3: bf16 C");
@@ -546,7 +548,17 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
   if constexpr (AFF8) Cb = (CT*)p.C;          // batch 1, no group, c_mode 0; may be null
   else Cb = (p.ngroup ? (CT*)p.grp.C[batch] : (CT*)p.C + (long long)batch * p.c_bs) +
             (p.c_mode == 3 ? (long long)split * p.slab : 0);
-  u32x4 xnx[(smode == 2 || PFC || AFF) ? IT * PQ : 1];   // the next staging pass's rows
+  // 16-B chunks a thread prefetches per pass: rows of C's type, or (ADD) two fp32 pieces per row
+  constexpr int NPF = (smode == 2 || PFC || AFF) ? IT * PQ : ADD ? IT * 2 : 1;
+  u32x4 xnx[NPF];                             // the next staging pass's rows
+  [[maybe_unused]] unsigned oknx = 0;         // ADD: bit it = row it of that pass was prefetched
+  // ADD: the addend row of output row `row` (< M): its block's frame through the map, one read
+  [[maybe_unused]] auto add_row = [&](int row) -> const float* {
+    int j, r;
+    fdivmod(row, p.add_div, j, r);
+    const int f = p.add_map ? p.add_map[j] : j;
+    return p.add + ((long long)f * p.add_rows + r) * p.add_ld;
+  };
   // write-through C stores (p.wt): the block's rows from its first one, 32-bit offsets
   // (AFF8 stores through pointers only: no descriptor is formed from a C that may be null)
   const __amdgpu_buffer_rsrc_t crs = buf_rsrc(AFF8 ? (CT*)nullptr : Cb + (long long)m0 * p.ldc);
@@ -571,6 +583,19 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
         const bool ok = p.br_x && row < p.M && col + 8 <= p.N && ((uintptr_t)src % 16 == 0);
 #pragma unroll
         for (int q = 0; q < PQ; ++q) xnx[it * PQ + q] = ok ? ((const u32x4*)src)[q] : u32x4{0u, 0u, 0u, 0u};
+      } else if constexpr (ADD) {
+        // the fp32 addend rows, two 16-byte pieces per 8 columns; a row the 16-byte loads cannot
+        // take (the tile's ragged edge, a misaligned view) is read element-wise by the store loop
+        if (it == 0) oknx = 0;
+        bool ok = row < p.M && col + 8 <= p.N;
+        const float* src = p.add;
+        if (ok) {
+          src = add_row(row) + col;
+          ok = (uintptr_t)src % 16 == 0;
+        }
+        xnx[2 * it] = ok ? ((const u32x4*)src)[0] : u32x4{0u, 0u, 0u, 0u};
+        xnx[2 * it + 1] = ok ? ((const u32x4*)src)[1] : u32x4{0u, 0u, 0u, 0u};
+        oknx |= (ok ? 1u : 0u) << it;
       }
     }
   };
@@ -581,9 +606,12 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
   // (AFF8: the 2-stage 128 x 128 tile on the two conv gathers keeps the plain fp8 kernel's two
   // blocks per CU only within 128 VGPRs, where the prefetch and the scale / shift values live
   // across the K loop spill 2-3 registers: those two fetch at the start of the pass)
+  // (ADD: two fp32 pieces per row and 8 columns, IT * 8 VGPRs; every tile but the 256 x 256 ones,
+  // which spill 5-11 registers with them live across the K loop)
+  constexpr bool ADD_EARLY = BM * BN < 256 * 256;
   constexpr bool EARLY = PFC || (AFF && !(LA == L_KC_CONV_G && BM * BN == 256 * 256 && PP == 1) &&
                                  !(AFF8 && LA != L_KC_DENSE && BM * BN == 128 * 128 && S == 2)) ||
-                         (smode == 2 && S >= 3 && BM * BN <= 128 * 128);
+                         (smode == 2 && S >= 3 && BM * BN <= 128 * 128) || (ADD && ADD_EARLY);
   float bk1[8], bsf[8], bmu[8];
   float fsc[8], fsh[8];   // AFF: this thread's eight folded scale / shift values
   auto epi_fold = [&]() {
@@ -611,7 +639,7 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
   if constexpr (AFF8) { if (p.c8) qinv = p.q_state[1]; }
   if constexpr (EARLY) {
     if constexpr (smode == 2) epi_affine();
-    if constexpr (AFF) epi_fold();
+    if constexpr (AFF || ADD) epi_fold();
     epi_fetch(0);
   }
 
@@ -853,21 +881,24 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
   int segA_end = 0x7fffffff;
   if constexpr (smode == 1) segA_end = (m0 / p.st_seg_rows + 1) * p.st_seg_rows;
   if constexpr (smode == 2 && !EARLY) epi_affine();
-  if constexpr (AFF && !EARLY) epi_fold();
+  if constexpr ((AFF || ADD) && !EARLY) epi_fold();
 #pragma unroll 1
   for (int pass = 0; pass < BM / HR; ++pass) {
     // EARLY: this pass's rows were prefetched (before the K loop / during the previous pass) and
     // the next pass's loads go out now.  Otherwise this pass's loads go out now, in flight while
     // the accumulators are staged through LDS.
-    u32x4 xpf[(smode == 2 || PFC || AFF) ? IT * PQ : 1];
+    u32x4 xpf[NPF];
+    [[maybe_unused]] unsigned okpf = 0;
     if constexpr (EARLY) {
 #pragma unroll
-      for (int i = 0; i < IT * PQ; ++i) xpf[i] = xnx[i];
+      for (int i = 0; i < NPF; ++i) xpf[i] = xnx[i];
+      if constexpr (ADD) okpf = oknx;
       if (pass + 1 < BM / HR) epi_fetch(pass + 1);
-    } else if constexpr (smode == 2 || AFF) {
+    } else if constexpr (smode == 2 || AFF || ADD) {
       epi_fetch(pass);
 #pragma unroll
-      for (int i = 0; i < IT * PQ; ++i) xpf[i] = xnx[i];
+      for (int i = 0; i < NPF; ++i) xpf[i] = xnx[i];
+      if constexpr (ADD) okpf = oknx;
     }
     {
       const int g = lane >> 4;
@@ -931,6 +962,25 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
         for (int e = 0; e < 8; ++e) {
           float t = fmaf(v[e], fsc[e], fsh[e]);
           if (p.br_x) t += q[e];
+          if (p.act == 1) t = fmaxf(t, 0.f);
+          else if (p.act == 2) t = t > 0.f ? t : slope * t;
+          v[e] = t;
+        }
+      }
+      if constexpr (ADD) {   // t = fma(acc + bias + add, scale, shift), then the activation
+        float q[8];
+        if ((okpf >> it) & 1u) {   // prefetched
+          *(u32x4*)&q[0] = xpf[2 * it];
+          *(u32x4*)&q[4] = xpf[2 * it + 1];
+        } else {
+          const float* as = add_row(row) + col;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) q[e] = (col + e < p.N) ? as[e] : 0.f;
+        }
+        const float slope = p.act == 2 ? p.prelu[0] : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float t = fmaf(v[e] + q[e], fsc[e], fsh[e]);
           if (p.act == 1) t = fmaxf(t, 0.f);
           else if (p.act == 2) t = t > 0.f ? t : slope * t;
           v[e] = t;
@@ -1398,7 +1448,17 @@ int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb,
     if (a.st_mode == 4 && (a.ngroup || c_f32 != (dtype == DT_F32) || !a.br_gamma || !a.br_beta ||
                            a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu)))
       return CN_ERR_UNSUPPORTED;
-    if (a.st_mode < 1 || a.st_mode == 3 || a.st_mode > 4) return CN_ERR_UNSUPPORTED;
+    if (a.st_mode < 1 || a.st_mode == 3 || a.st_mode > 5) return CN_ERR_UNSUPPORTED;
+    if (a.st_mode == 5) {
+      // the addend epilogue: the plain product and the one-tap-per-K-tile conv gather only (the
+      // per-thread-pointer gather is not instantiated: refused, not replaced)
+      if (a.ngroup || c_f32 != (dtype == DT_F32) || !a.br_gamma || !a.br_beta || !a.add || a.add_rows <= 0 ||
+          a.M % a.add_rows || a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu) || la == L_KC_CONV_G)
+        return CN_ERR_UNSUPPORTED;
+      if (dtype == DT_BF16)
+        return la == L_KC_DENSE ? launch_epi<bf16, L_KC_DENSE, 5>(a, batch, st) : launch_epi<bf16, L_KC_CONV, 5>(a, batch, st);
+      return la == L_KC_DENSE ? launch_epi<float, L_KC_DENSE, 5>(a, batch, st) : launch_epi<float, L_KC_CONV, 5>(a, batch, st);
+    }
 #define CN_EPI(T_, M_) \
     return la == L_KC_DENSE ? launch_epi<T_, L_KC_DENSE, M_>(a, batch, st) : \
            la == L_KC_CONV ? launch_epi<T_, L_KC_CONV, M_>(a, batch, st) : launch_epi<T_, L_KC_CONV_G, M_>(a, batch, st)

@@ -101,7 +101,9 @@ class FeatureBank:
     f*HW .. f*HW + HW - 1; geo = (T, h, w) and input_size = (H, W).  coatt = "mxfp8" adds mx / dmx,
     the MX-fp8 images of (vat, va) / (dat, da) (ops.coatt_f8_bank: each frame quantised once, about
     2.9 MB per frame and modality at 473 x 473), and head_a_indexed then runs the fp8 co-attention
-    over them; the default "bf16" leaves both None."""
+    over them; the default "bf16" leaves both None.  partials (reduce_partials: the split head's
+    per-frame products, fp32, 3.7 MB per frame and modality at 473 x 473) is None until first asked
+    for."""
 
     COATT = ("bf16", "mxfp8")
 
@@ -110,10 +112,41 @@ class FeatureBank:
         self.geo = tuple(geo)
         self.input_size = tuple(input_size)
         self.mx, self.dmx = mx, dmx
+        self.partials = None
 
     @property
     def n_frames(self):
         return self.geo[0]
+
+    @torch.no_grad()
+    def reduce_partials(self, model, frame_chunk=8):
+        """(ua, uda), fp32 [T*HW][256]: the pass-through half of each modality's reduce conv over
+        the bank's frames, conv_fwd_partial(va, W[..., C:]) (cosnet_amd/head_split.py) -- the fp32
+        accumulator, unrounded, which head_a_indexed(split=True) adds per pair through its map.
+        Runs in chunks of frame_chunk whole frames (a frame's rows do not depend on the chunking);
+        computed on first use and kept on the bank."""
+        if self.partials is not None:
+            return self.partials
+        hs = getattr(model, "head_split", None)
+        if hs is None:
+            raise RuntimeError("reduce_partials: model.set_head_split() first")
+        if frame_chunk < 1:
+            raise ValueError("reduce_partials: frame_chunk >= 1 is expected")
+        from .head_split import reduce_sides
+        t, h, w = self.geo
+        hw = h * w
+        outs = []
+        for v, (reduce, _) in zip((self.va, self.da), reduce_sides(model)):
+            _, wv = hs.halves(reduce, v.dtype)
+            cout = reduce.weight.shape[0]
+            u = torch.empty((t * hw, cout), dtype=torch.float32, device=v.device)
+            for f0 in range(0, t, frame_chunk):
+                f1 = min(t, f0 + frame_chunk)
+                ops.conv_fwd_partial(v[f0 * hw:f1 * hw], f1 - f0, h, w, wv, cout, 3, 1, 1, 1,
+                                     out=u[f0 * hw:f1 * hw])
+            outs.append(u)
+        self.partials = tuple(outs)
+        return self.partials
 
     @staticmethod
     def _similarity(feats, linear):
@@ -191,13 +224,17 @@ class FeatureBank:
 
 @torch.no_grad()
 def segment_sequence(model, rgbs, depths, refs, targets=None, encode_chunk=8, pair_chunk=10,
-                     coatt="bf16"):
+                     coatt="bf16", head="cat"):
     """rgbs [T,3,H,W], depths [T,1,H,W] (fp32 NCHW on the GPU), refs [Tt][N] and targets [Tt]
     (default: every frame in order) frame indices -> [Tt,1,H,W] fp32 whose row t is
     multi_reference_x1(model, rgbs[t], depths[t], rgbs[refs[t]], depths[refs[t]]) up to rounding:
     every frame is encoded once and the a-side head runs over chunks of whole targets of about
     pair_chunk pairs.  coatt = "mxfp8" (bf16 models): the co-attention runs on MX-fp8 images of
-    the bank (FeatureBank); "bf16" (default): the bf16 indexed kernel."""
+    the bank (FeatureBank); "bf16" (default): the bf16 indexed kernel.  head = "split"
+    (model.set_head_split()): the reduce convs run split by input-channel half, the pass-through
+    half once per frame (cosnet_amd/head_split.py); "cat" (default): over the concat, per pair."""
+    if head not in ("cat", "split"):
+        raise ValueError("head: 'cat' or 'split' is expected, not %r" % (head,))
     t = rgbs.shape[0]
     if targets is None:
         targets = list(range(t))
@@ -210,7 +247,7 @@ def segment_sequence(model, rgbs, depths, refs, targets=None, encode_chunk=8, pa
     step = max(1, int(pair_chunk) // n)   # whole targets per head call
     for t0 in range(0, nt, step):
         t1 = min(nt, t0 + step)
-        x1 = model.head_a_indexed(bank, ia[t0 * n:t1 * n], ib[t0 * n:t1 * n])
+        x1 = model.head_a_indexed(bank, ia[t0 * n:t1 * n], ib[t0 * n:t1 * n], split=head == "split")
         ops.mean_groups(x1.view((t1 - t0) * n, hw), t1 - t0, n, out=out[t0:t1].view(t1 - t0, hw))
     return out
 

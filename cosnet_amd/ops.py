@@ -309,6 +309,98 @@ def conv_fwd_affine(x, n, h, w, wf, cout, k, stride, pad, dil, scale, shift, act
     return out, g.oh, g.ow
 
 
+def conv_fwd_partial(x, n, h, w, wf, cout, k, stride, pad, dil, bias=None, out=None):
+    """The unrounded product of a forward conv (cn_conv_fwd_partial): x [n*h*w, >=cin] in bf16 or
+    fp32 -> (y fp32 [n*oh*ow, cout] or `out`, oh, ow) holding the fp32 accumulator (+ bias): one
+    term of a conv split by input channels, for conv_fwd_affine_add to add."""
+    g, out, args = _fwd_conv(x, n, h, w, wf, cout, k, stride, pad, dil, bias, out, torch.float32)
+    if out.dtype != torch.float32:
+        raise ValueError("conv_fwd_partial: the output is fp32")
+    with _profiled(_fwd_record, "fwd_partial", g, x.element_size(), 4):
+        nv.call("cn_conv_fwd_partial", dtc(x), *args, nv.stream())
+    return out, g.oh, g.ow
+
+
+def _fwd_affine_add_record(tag, g, es, nadd):
+    """The folded conv with its fp32 addend rows read once per frame they belong to."""
+    fl, tg, nb = _fwd_record(tag, g, es, es)
+    return fl, tg, nb + 4 * nadd
+
+
+def conv_fwd_affine_add(x, n, h, w, wf, cout, k, stride, pad, dil, scale, shift, add, add_rows, add_map=None,
+                        act=0, prelu=None, bias=None, out=None):
+    """y = act(fma(conv(x) + bias + add[f], scale, shift)) in one launch (cn_conv_fwd_affine_add):
+    conv_fwd_affine whose epilogue first adds fp32 rows looked up per block of add_rows output rows
+    -- block j of y takes rows f*add_rows .. of `add`, f = add_map[j] (int32 on the GPU; None: j).
+    add: fp32 [F*add_rows, >=cout] (conv_fwd_partial's output over a bank of F frames).
+    x [n*h*w, >=cin] -> (y [n*oh*ow, cout] or `out`, oh, ow)."""
+    g, out, args = _fwd_conv(x, n, h, w, wf, cout, k, stride, pad, dil, bias, out, x.dtype)
+    if add is not None and add.dtype != torch.float32:
+        raise ValueError("conv_fwd_affine_add: add is fp32")
+    for t in (scale, shift):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != cout or t.stride(0) != 1:
+            raise ValueError("conv_fwd_affine_add: scale / shift are fp32 [%d] arrays" % cout)
+    add_rows = int(add_rows)
+    nblk = g.M // add_rows if add_rows > 0 and g.M % add_rows == 0 else 0   # the library refuses the rest
+    if add_map is not None and nblk:
+        _idx(add_map, nblk)
+    nadd = 0 if add is None else min(add.shape[0], g.M) * cout
+    with _profiled(_fwd_affine_add_record, "fwd_affine_add", g, x.element_size(), nadd):
+        nv.call("cn_conv_fwd_affine_add", dtc(x), *args, scale.data_ptr(), shift.data_ptr(), *_mat(add, 0),
+                nv.ptr(add_map), add_rows, int(act), nv.ptr(prelu), nv.stream())
+    return out, g.oh, g.ow
+
+
+def weight_halves(wf, k, out=None):
+    """The two input-channel halves of a forward conv weight wf [Cout][k*k*2C] (= [Cout][k][k][2C]):
+    (W[..., :C], W[..., C:]), each contiguous [Cout][k*k*C] in wf's dtype -- conv(W, [a | b]) =
+    conv(W[..., :C], a) + conv(W[..., C:], b).  `out`: a [2, Cout, k*k*C] tensor to fill in place."""
+    cout, kk = wf.shape[0], k * k
+    c2 = wf.shape[1] // kk
+    if wf.shape[1] != kk * c2 or c2 % 2:
+        raise ValueError("weight_halves: a [Cout][%d*%d*2C] weight is expected" % (k, k))
+    c = c2 // 2
+    if out is None:
+        out = torch.empty((2, cout, kk * c), dtype=wf.dtype, device=wf.device)
+    rows = wf.view(cout * kk, c2)
+    for i in range(2):
+        src, dst = rows[:, i * c:(i + 1) * c], out[i].view(cout * kk, c)
+        if wf.is_cuda:
+            cast_copy(src, dst)
+        else:
+            dst.copy_(src)
+    return out[0], out[1]
+
+
+class HalfWeightCache:
+    """weight_halves of the compute-dtype forward copy of a conv weight (WCACHE.get), under
+    WeightCache's rule: one entry per (parameter, dtype) whose storage is allocated once and never
+    replaced, valid while the parameter's tag (version counter, epoch, data pointer) matches and
+    rewritten IN PLACE when it does not."""
+
+    def __init__(self):
+        self._c = {}
+
+    def get(self, w, dtype):
+        key = (id(w), tuple(w.shape), dtype)
+        hit = self._c.get(key)
+        tag = WeightCache._tag(w)
+        if hit is not None and hit[0] == tag:
+            return hit[1][0], hit[1][1]
+        wf, _ = WCACHE.get(w, dtype, need_t=False)
+        if hit is None:
+            kk = w.shape[2] * w.shape[3]
+            buf = torch.empty((2, w.shape[0], kk * (w.shape[1] // 2)), dtype=dtype, device=w.device)
+            hit = [None, buf, weakref.ref(w, lambda _r, k=key: self._c.pop(k, None))]
+            self._c[key] = hit
+        weight_halves(wf, w.shape[2], out=hit[1])
+        hit[0] = tag
+        return hit[1][0], hit[1][1]
+
+
+HCACHE = HalfWeightCache()
+
+
 def bn_fold_table(bn, out=None):
     """(scale, shift) fp32 [C] of an eval-mode BatchNorm2d (cn_bn_fold_table): the affine bn_apply
     forms from the running statistics on every call, written once.  `out`: a [2, C] fp32 tensor
@@ -728,6 +820,16 @@ def gate_cat_idx(z, vbank, iv, p, hw, g, gb=None, out=None):
         out = torch.empty((p * hw, 2 * c), dtype=z.dtype, device=z.device)
     nv.call("cn_gate_cat_idx", dtc(z), *_mat(z), *_mat(vbank), _idx(iv, p), p, hw, c,
             g.reshape(-1).data_ptr(), nv.ptr(gb), *_mat(out), nv.stream())
+    return out
+
+
+def gate_fwd(z, g, gb=None, out=None):
+    """out = z * sigmoid(z . g + gb) per row (cn_gate_fwd; rgbd_segmentation_RAA.py:177-184,
+    :228-235): the gated half of gate_cat_idx's rows on its own, [P, C] in z's dtype."""
+    if out is None:
+        out = torch.empty((z.shape[0], z.shape[1]), dtype=z.dtype, device=z.device)
+    nv.call("cn_gate_fwd", dtc(z), *_mat(z), z.shape[0], z.shape[1], g.reshape(-1).data_ptr(), nv.ptr(gb),
+            *_mat(out), None, nv.stream())
     return out
 
 

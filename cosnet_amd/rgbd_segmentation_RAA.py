@@ -61,6 +61,7 @@ class RGBDSegmentation_RAA(nn.Module):
         self.fp8 = None            # Fp8Context: e4m3 forward conv GEMMs in the encoders (configs[4])
         self.fp8_static = None     # Fp8Static: frozen-scale e4m3 encoders for inference (set_fp8_static)
         self.bn_fold = None        # BnFold: eval-mode BN folded into the conv GEMMs (set_bn_fold)
+        self.head_split = None     # HeadSplit: the head's reduce convs split by channel half (set_head_split)
         self.pair_encoder = True   # batch frames a and b through each encoder (encoder_fn.py)
         # depth encoder on a second stream (forward()); CN_CONCURRENT_ENCODERS=0 for A/B runs
         self.concurrent_encoders = os.environ.get("CN_CONCURRENT_ENCODERS", "1") != "0"
@@ -226,6 +227,27 @@ class RGBDSegmentation_RAA(nn.Module):
         self.depth_encoder._cn_bn_fold = st.encoders["depth_encoder"]
         return self
 
+    def set_head_split(self, on=True):
+        """The a-side head's two reduce convs split by input-channel half for whole-sequence
+        inference (cosnet_amd/head_split.py): conv(W, [gate(Z_a) | V_a]) = conv(W[..., :C], gate(Z_a))
+        + conv(W[..., C:], V_a), and the second term depends on the target frame alone.  With it set,
+        segment_sequence(head="split") / head_a_indexed(split=True) compute that term once per frame
+        of the bank (FeatureBank.reduce_partials, cn_conv_fwd_partial) and add it in the epilogue of
+        the per-pair half-width conv, in front of the eval-mode BN and the one rounding
+        (cn_conv_fwd_affine_add); the [P*HW][2C] concat is never written.  The weight halves and the
+        (scale, shift) tables of bn_A / depth_bn are built now and follow later changes of their
+        tensors; the tables are those of set_bn_fold / set_fp8_static(fold_bn=True) while either is
+        active.  Needs eval mode; bf16 and fp32; composes with set_bn_fold and set_fp8_static.  The
+        default head is untouched; False switches it off."""
+        if not on:
+            self.head_split = None
+            return self
+        if self.training:
+            raise RuntimeError("set_head_split: the folded BN uses running statistics (eval mode)")
+        from .head_split import HeadSplit
+        self.head_split = HeadSplit(self)
+        return self
+
     def _set_dtype(self):
         for m in self.modules():
             m._cn_dtype = self.compute_dtype
@@ -328,7 +350,7 @@ class RGBDSegmentation_RAA(nn.Module):
         dz_a, dz_b = self._depth_head(da, db, geo)
         return self._decode(z_a, z_b, dz_a, dz_b, geo, input_size)
 
-    def head_a_indexed(self, bank, ia, ib):
+    def head_a_indexed(self, bank, ia, ib, split=False):
         """The a side of head_nhwc for pairs of frames of one feature bank
         (cosnet_amd.inference.FeatureBank): pair p co-attends frame ia[p] (a role) with frame
         ib[p] (b role); ia / ib int32[P] (CPU or GPU) -> x1 [P,1,H,W] fp32.  test.py:287-305 uses
@@ -341,11 +363,16 @@ class RGBDSegmentation_RAA(nn.Module):
         under no_grad; the model's own fp8 mode (set_fp8: fp8 encoder convs with delayed scaling,
         whose features depend on the order of calls) stays refused.  Static fp8 (set_fp8_static:
         frozen scales, so a frame's features depend on the frame alone) is accepted: its bank is
-        four bf16 tensors like any other."""
+        four bf16 tensors like any other.  split=True (model.set_head_split()): the reduce conv
+        runs on the gated half alone and adds the a-role frame's partial (bank.reduce_partials) in
+        its epilogue, BN folded; there is no concat.  Equal to the default head up to rounding."""
         if self.training or torch.is_grad_enabled():
             raise RuntimeError("head_a_indexed is an inference path: eval mode under torch.no_grad()")
         if getattr(self, "fp8", None) is not None:
             raise RuntimeError("head_a_indexed: fp8 banks are not supported (set_fp8(False))")
+        hs = getattr(self, "head_split", None)
+        if split and hs is None:
+            raise RuntimeError("head_a_indexed(split=True): model.set_head_split() first")
         fold = getattr(self, "bn_fold", None)   # set_bn_fold: the reduce conv and its BN in one launch
         if fold is None and getattr(getattr(self, "fp8_static", None), "head", None) is not None:
             fold = self.fp8_static   # set_fp8_static(fold_bn=True): the same bf16 launch, its own tables
@@ -369,16 +396,32 @@ class RGBDSegmentation_RAA(nn.Module):
         mx = bank.mx   # MX-fp8 images (bf16 features, C = 256 by construction)
         if (mx is None) != (bank.dmx is None):
             raise ValueError("head_a_indexed: an MX-fp8 bank holds the images of both modalities (mx and dmx)")
-        if indexed or mx is not None:
+        if indexed or mx is not None or split:
             ia_d, ib_d = ia.to(dev).contiguous(), ib.to(dev).contiguous()
-        else:
+        if not (indexed or mx is not None):
             ia_h, ib_h = ia.tolist(), ib.tolist()
+        if split:   # the pass-through halves' products, once per frame of the bank
+            partials = bank.reduce_partials(self)
         if mx is not None:   # both modalities' Z_a in one launch
             zas = [torch.empty((p * hw, bank.va.shape[1]), dtype=torch.bfloat16, device=dev) for _ in sides]
             ops.coatt_f8_idx(mx, bank.dmx, t, ia_d, ib_d, p, hw, zas[0], zas[1])       # :160-170, :213-221
         zs = []
         for k, (v, vt, gate, reduce, bn) in enumerate(sides):
             c = v.shape[1]
+            if split:
+                if mx is not None:
+                    za = zas[k]
+                elif indexed:
+                    za = torch.empty((p * hw, c), dtype=v.dtype, device=dev)
+                    ops.coatt_fused_idx(vt, v, v, ia_d, ib_d, p, hw, za=za, zb=None)       # :160-170
+                else:
+                    za = fn.coatt_a_materialised(_gather_frames(vt, ia_h, hw), _gather_frames(v, ib_h, hw), p, hw)
+                gz = ops.gate_fwd(za, gate.weight, gate.bias)                               # :177-184
+                wz, _ = hs.halves(reduce, v.dtype)
+                sc, sf = hs.tables().get(bn)
+                zs.append(ops.conv_fwd_affine_add(gz, p, h, w, wz, reduce.weight.shape[0], 3, 1, 1, 1, sc, sf,
+                                                  partials[k], hw, add_map=ia_d)[0])       # :186-190
+                continue
             if mx is not None:
                 cat = ops.gate_cat_idx(zas[k], v, ia_d, p, hw, gate.weight, gate.bias)  # :177-186
             elif indexed:

@@ -19,7 +19,9 @@ sequence's frames are loaded and encoded ONCE and the pairs are formed by index
 (cosnet_amd.inference.segment_sequence); same log lines, order and PNGs.  With it,
 `--coatt mxfp8` (bf16 only) runs the bank's co-attention on MX-fp8 images of the features, and
 `--dtype fp8 [--fp8-calibration FILE]` runs the encoders' conv GEMMs on e4m3 operands under
-calibrated, frozen scales (cosnet_amd/fp8_infer.py); the two compose.
+calibrated, frozen scales (cosnet_amd/fp8_infer.py); the two compose.  `--split-reduce` runs the
+head's reduce convs split by input-channel half, the pass-through half once per frame
+(model.set_head_split(), segment_sequence(head="split")); it composes with all of the above.
 """
 import argparse
 import datetime
@@ -67,6 +69,10 @@ def get_arguments(argv=None):
                    help="--feature-bank --dtype fp8: every fp8 conv + eval-mode BatchNorm pair of the encoders as "
                         "one launch (cn_conv_fwd_fp8_affine) and the head's reduce convs folded "
                         "(model.set_fp8_static(calibration, fold_bn=True))")
+    p.add_argument("--split-reduce", action="store_true",
+                   help="--feature-bank: the head's 3x3 reduce convs split by input-channel half -- the "
+                        "pass-through half V_a once per frame, the gated half per pair with that partial added "
+                        "in the GEMM epilogue (model.set_head_split(), segment_sequence(head='split'))")
     p.add_argument("--fp8-calibration", default=None, metavar="FILE",
                    help="--dtype fp8: the calibration (JSON).  Loaded if the file exists; otherwise made "
                         "before evaluation from the first --fp8-calibration-frames test frames and written there")
@@ -84,6 +90,8 @@ def get_arguments(argv=None):
         p.error("--fold-bn runs the bf16 / fp32 encoders (not --dtype fp8)")
     if args.fp8_fold_bn and not (args.feature_bank and args.dtype == "fp8"):
         p.error("--fp8-fold-bn needs --feature-bank --dtype fp8")
+    if args.split_reduce and not args.feature_bank:
+        p.error("--split-reduce needs --feature-bank")
     if args.dtype == "fp8" and args.fp8_calibration_frames < 1:
         p.error("--fp8-calibration-frames must be at least 1")
     if args.dtype != "fp8" and args.fp8_calibration:
@@ -151,6 +159,9 @@ def main(argv=None):
     model.to(dev)
     if args.fold_bn:
         model.set_bn_fold()
+    if args.split_reduce:
+        model.set_head_split()
+    head = "split" if args.split_reduce else "cat"
 
     out_dir = None
     if str(args.save_seg_img) not in ("False", "0", ""):
@@ -221,7 +232,8 @@ def main(argv=None):
                 x1 = segment_sequence(model, torch.stack([l[0] for l in loaded]),
                                       torch.stack([l[1] for l in loaded]),
                                       [[pos[f] for f in pl[1:]] for pl in plans[k:k1]],
-                                      targets=[pos[pl[0]] for pl in plans[k:k1]], coatt=args.coatt)
+                                      targets=[pos[pl[0]] for pl in plans[k:k1]], coatt=args.coatt,
+                                      head=head)
                 for i in range(k, k1):
                     if i % args.batch_size == 0:
                         print("%d processd" % (i // args.batch_size))
@@ -252,7 +264,7 @@ def main(argv=None):
                 # synthetic frames belong to no sequence: a bank of the target and its own references
                 x1 = segment_sequence(model, torch.cat([tgt, srch]), torch.cat([tdep, sdep]),
                                       [list(range(1, args.sample_range + 1))], targets=[0],
-                                      coatt=args.coatt)
+                                      coatt=args.coatt, head=head)
             else:
                 x1 = multi_reference_x1(model, tgt, tdep, srch, sdep)      # [1,1,h,w]
             emit(x1, batch["target_gt"][j:j + 1], batch["seq_name"][j], batch["frame_index"][j])

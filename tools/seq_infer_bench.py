@@ -23,6 +23,11 @@ runs of this tool with --coatt bf16 and --coatt mxfp8 on one device.
 calibrated on the tool's own sequence before timing; the per-target path stays bf16 and the result
 also holds the fp8 bank's outputs against the bf16 bank's.  Alternate runs with --dtype bf16 and
 --dtype fp8 to compare.
+
+--head split runs the bank path's head with the reduce convs split by input-channel half
+(model.set_head_split, cosnet_amd/head_split.py; composes with every setting above); the result
+then also holds its outputs against the default ("cat") head's in the same setting.  Alternate runs
+with --head cat and --head split to compare.
 """
 import argparse
 import json
@@ -64,6 +69,9 @@ def parse():
     ap.add_argument("--fp8-fold-bn", action="store_true",
                     help="--dtype fp8: eval-mode BN folded into the static-scale fp8 conv GEMMs "
                          "(model.set_fp8_static(calibration, fold_bn=True))")
+    ap.add_argument("--head", default="cat", choices=["cat", "split"],
+                    help="the bank path's head: cat (default), the reduce convs over the concat per pair; split, "
+                         "their pass-through half once per frame (model.set_head_split)")
     a = ap.parse_args()
     if a.fold_bn and a.dtype == "fp8":
         ap.error("--fold-bn runs the bf16 / fp32 encoders")
@@ -152,6 +160,9 @@ def main():
         fold = m.set_bn_fold().bn_fold
         m.set_bn_fold(False)
 
+    if a.head == "split":   # the weight halves (and tables) are built once, here
+        m.set_head_split()
+
     def with_static(fn):
         if fold is not None:
             m.set_bn_fold(fold)
@@ -169,7 +180,7 @@ def main():
 
     def bank():
         return with_static(lambda: segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk,
-                                                    pair_chunk=a.pair_chunk, coatt=a.coatt))
+                                                    pair_chunk=a.pair_chunk, coatt=a.coatt, head=a.head))
 
     # ---- stage split: the same calls with events between the stages -------------------------------
     @torch.no_grad()
@@ -209,11 +220,11 @@ def main():
             out = torch.empty((T, H * H), dtype=torch.float32, device=dev)
             for t0 in range(0, T, step):
                 t1 = min(T, t0 + step)
-                x1 = m.head_a_indexed(b, ia[t0 * N:t1 * N], ib[t0 * N:t1 * N])
+                x1 = m.head_a_indexed(b, ia[t0 * N:t1 * N], ib[t0 * N:t1 * N], split=a.head == "split")
                 ops.mean_groups(x1.view((t1 - t0) * N, H * H), t1 - t0, N, out=out[t0:t1])
             return out
 
-        st.run("head", head)
+        st.run("head", lambda: with_static(head))
 
     m._set_dtype()
     for _ in range(max(1, a.warmup)):   # every shape of the timed window, both paths
@@ -260,13 +271,20 @@ def main():
         extra["fold_vs_default_bank"] = {"mask_agreement": float(((fm > 0.5) == (ref > 0.5)).double().mean()),
                                          "mean_abs_diff": float((fm - ref).abs().mean()),
                                          "max_abs_diff": float((fm - ref).abs().max())}
+    if a.head == "split":   # the split head against the default head, every other setting the same
+        ref = with_static(lambda: segment_sequence(m, rgbs, deps, refs, encode_chunk=a.encode_chunk,
+                                                   pair_chunk=a.pair_chunk, coatt=a.coatt)).double().cpu()
+        fm = out_b.double().cpu()
+        extra["split_vs_cat_head"] = {"mask_agreement": float(((fm > 0.5) == (ref > 0.5)).double().mean()),
+                                      "mean_abs_diff": float((fm - ref).abs().mean()),
+                                      "max_abs_diff": float((fm - ref).abs().max())}
     fa, fb = out_a.double().cpu(), out_b.double().cpu()
     stat = lambda v: {"mean": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v)),
                       "spread": float((np.max(v) - np.min(v)) / np.mean(v))}
     ma, mb = float(np.mean(ta)), float(np.mean(tb))
     res = {
         "tool": "seq_infer_bench", "frames": T, "nref": N, "size": H, "dtype": a.dtype, "coatt": a.coatt,
-        "fold_bn": bool(a.fold_bn), "fp8_fold_bn": bool(a.fp8_fold_bn),
+        "fold_bn": bool(a.fold_bn), "fp8_fold_bn": bool(a.fp8_fold_bn), "head": a.head,
         "seed": a.seed, "rounds": a.rounds, "warmup": max(1, a.warmup), "encode_chunk": a.encode_chunk,
         "pair_chunk": a.pair_chunk, "device": torch.cuda.get_device_name(0),
         "per_target": {"frames_per_s": T / (ma * 1e-3), "ms_per_sequence": stat(ta),
