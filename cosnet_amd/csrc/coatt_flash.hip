@@ -242,7 +242,10 @@ void coatt_flash_dvat_k(BwdArgs a) {
     }
 
     // ---- dS^T (register i: key 32t + (i&3) + 8(i>>2) + 4h) -> bf16 B operand.  Keys past HW
-    // have zero Vb rows in the transposed image, so whatever dS they get contributes nothing.
+    // have zero Vb rows in the transposed image, but their dS must be zero all the same: S is 0
+    // there, so P0 = exp2(-lse_a) overflows for a row whose logits all lie below ~-88
+    // (lse_a < -128), and inf x 0 in the product below would turn the whole row NaN.
+    const int kleft = HW - (tb + t) * BK - 4 * h;   // keys i with (i&3) + 8(i>>2) < kleft are real
     bf16x8 pf[2];
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
@@ -254,7 +257,7 @@ void coatt_flash_dvat_k(BwdArgs a) {
         if constexpr (T0) x = __builtin_amdgcn_exp2f(fmaf(s[i], L2E, -lsea)) * (p0[i] - dd0);
         if constexpr (T1)
           x = fmaf(__builtin_amdgcn_exp2f(fmaf(s[i], L2E, -nk[i >> 2][i & 3])), p1[i] - nd[i >> 2][i & 3], x);
-        dv[j] = x;
+        dv[j] = (i & 3) + 8 * (i >> 2) < kleft ? x : 0.f;
       }
       pf[s2] = pack8b(dv);
     }
