@@ -211,6 +211,27 @@ int cn_gemm(int dtype, int layout_a, int layout_b, int M, int N, int K, int ka_l
 /* x holds nseg segments of P rows each (frames a and b of a siamese pair, each its own BN
  * batch as in the reference's two encoder calls, rgbd_segmentation_RAA.py:143-148, 198-203);
  * mean/invstd are [nseg][C]; running stats are updated segment after segment. */
+/* Rounding and bounds contract of cn_bn_stats, cn_bn_apply*, cn_bn_bwd and cn_bn_bwd_apply
+ * (tests/test_gpu_bn_exact.py pins it bitwise on inputs whose every intermediate is exact):
+ *   - y, dx and dres are ONE round-to-nearest-even rounding of the fp32 value: the activation
+ *     t = act(fma(x, gamma*invstd, beta - mean*gamma*invstd) [+ res] [+ the same affine of xr]),
+ *     dz = dy * mask, and dx = gamma*invstd*(dz - sum_dz/P - xhat*sum_dzxh/P); a residual or a
+ *     second BN is added before the rounding, never after it
+ *   - the fp8 copy y8 = e4m3(clamp(t * qstate[1], +-448)) and the amax (qstate[2] = max with
+ *     max |t|) are taken from the fp32 t, not from the rounded y; qstate[0], [1] and [3] are only
+ *     read
+ *   - the mask bits, and the ReLU mask of the backward's act 1, are `stored y > 0`; act 3 recomputes
+ *     the forward's fma from x (equal to act 1 and act 4 wherever no residual was added); a
+ *     pre-activation of exactly 0 is masked (dz = 0; PReLU: dz = a * dy)
+ *   - mean, invstd and the running statistics are float roundings of a double evaluation of the
+ *     fp32 shifted sums (exact sums give the correctly rounded statistics; running_var takes the
+ *     unbiased variance; the segments update the running statistics in order, each update
+ *     rounded to float)
+ *   - nothing outside [nseg*P, C] of an output view (base, ld) is written, y8 and the mask
+ *     (bytes [nseg*P, C / vec]) included
+ *   - no operand byte outside its view reaches a result: row padding and rows past the last may
+ *     hold anything, NaN included
+ *   (pinned on views with 16-byte aligned bases and ld % (4 fp32 | 8 bf16) == 0, ldy8 % 16 == 0) */
 size_t cn_bn_workspace_floats(int dtype, int P, int C, int nseg);
 int cn_bn_stats(int dtype, const void* x, long long ldx, int P, int nseg, int C, float* mean,
                 float* invstd, float* run_mean, float* run_var, float momentum, float eps,

@@ -22,9 +22,13 @@ column 16, ROWS_PAST rows after the last): the padding of the inputs is NaN (any
 the MACs turns the output NaN), the outputs are NaN inside the view before a store (the old C
 before an accumulation) and SENTINEL everywhere outside, which must come back bitwise.
 """
+import decimal
 import functools
+import math
+from fractions import Fraction
 from types import SimpleNamespace
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -652,8 +656,128 @@ def test_gemm_kb_lim_exact(cuda, dt):
 
 
 # ---- 6. BN-statistics epilogue --------------------------------------------------------------
-def check_bn_stats(y_ref, n, nseg, cout, mean, invstd, bn):
-    """test_conv_fwd_bn_epilogue_stats's tolerances, against fp64 statistics of the exact y."""
+# The statistics kernels sum in fp32 (exact on integer data below 2^24) and finish in double:
+# mean, invstd and the running statistics are float roundings of a double evaluation.  On exact
+# sums they equal the float rounding of the EXACT value wherever that value lies further from a
+# float32 rounding boundary than the double evaluation can err, which stats_reference proves per
+# channel on the CPU (the margin condition) -- so the comparison is bitwise.
+BN_MOMENTUM32 = float(torch.tensor(0.1, dtype=f32))    # the float arguments, widened to double
+BN_EPS32 = float(torch.tensor(1e-5, dtype=f32))
+MARGIN = 8                 # x the measured fp64-vs-exact difference
+ULP64 = 2.0 ** -52         # floor of that difference, relative: 2 ulp for a device sqrt / fma
+
+
+def _fma(a, b, c):
+    """One rounding of a * b + c, as a contracted device expression evaluates it."""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def _f32(v):
+    return float(np.float32(v))
+
+
+def round_f32_with_margin(exact, evals):
+    """(float32 rounding of the Fraction `exact`, margin condition holds): the distance of `exact`
+    to the nearer float32 rounding boundary must exceed MARGIN x the largest difference between
+    `exact` and the fp64 evaluations `evals` of the kernel's formula (at least 2 ulp of fp64)."""
+    r = _f32(float(exact))
+    lo = float(np.nextafter(np.float32(r), np.float32(-np.inf)))
+    hi = float(np.nextafter(np.float32(r), np.float32(np.inf)))
+    dist = min(abs(exact - (Fraction(lo) + Fraction(r)) / 2), abs(exact - (Fraction(hi) + Fraction(r)) / 2))
+    diff = max([abs(Fraction(e) - exact) for e in evals] + [abs(exact) * Fraction(ULP64)])
+    ok = dist > MARGIN * diff and all(_f32(e) == r for e in evals)
+    return r, ok
+
+
+def _exact_rsqrt(v):
+    """1 / sqrt(v) of a Fraction to 60 digits, as a Fraction."""
+    with decimal.localcontext() as ctx:
+        ctx.prec = 60
+        d = decimal.Decimal(v.numerator) / decimal.Decimal(v.denominator)
+        return Fraction(1 / d.sqrt())
+
+
+def stats_reference(s1, s2, n, shift, rm, rv, tile_form=False):
+    """Float32 statistics of one channel over its segments, from exact integer sums.
+
+    s1[g], s2[g]: sum (x - shift[g]) and sum (x - shift[g])^2 of segment g (Python ints), n rows a
+    segment, rm / rv the running statistics before (float32 values).  tile_form False mirrors
+    bn_stats_finalize (q = s2 - s1 * md, var = q / n, unbiased q / (n - 1)), True
+    bn_tile_stats_finalize (shift 0; var = s2 / n - md * md, unbiased var * n / (n - 1)); both in
+    double with and without fma contraction, the running update rounded to float per segment.
+    Returns (mean[g], invstd[g], running_mean, running_var, margin condition holds for all)."""
+    m, eps, ok = BN_MOMENTUM32, BN_EPS32, True
+    means, invstds = [], []
+    for g in range(len(s1)):
+        a, b, k = float(s1[g]), float(s2[g]), float(shift[g])
+        md = a / n
+        if tile_form:
+            vars64 = [max(b / n - md * md, 0.0), max(_fma(-md, md, b / n), 0.0)]
+            unb64 = [v * n / (n - 1) for v in vars64]
+        else:
+            qs = [max(b - a * md, 0.0), max(_fma(-a, md, b), 0.0)]
+            vars64, unb64 = [q / n for q in qs], [q / (n - 1) for q in qs]
+        mean64 = k + md
+        e_mean = Fraction(shift[g]) + Fraction(s1[g], n)
+        e_q = Fraction(s2[g]) - Fraction(s1[g]) ** 2 / n
+        e_var, e_unb = e_q / n, e_q / (n - 1)
+        r, o = round_f32_with_margin(e_mean, [mean64])
+        means.append(r)
+        ok &= o
+        r, o = round_f32_with_margin(_exact_rsqrt(e_var + Fraction(eps)), [1.0 / math.sqrt(v + eps) for v in vars64])
+        invstds.append(r)
+        ok &= o
+        e_rm = (1 - Fraction(m)) * Fraction(rm) + Fraction(m) * e_mean
+        rm, o = round_f32_with_margin(e_rm, [(1.0 - m) * rm + m * mean64, _fma(1.0 - m, rm, m * mean64),
+                                             _fma(m, mean64, (1.0 - m) * rm)])
+        ok &= o
+        e_rv = (1 - Fraction(m)) * Fraction(rv) + Fraction(m) * e_unb
+        ev = []
+        for u in unb64:
+            ev += [(1.0 - m) * rv + m * u, _fma(1.0 - m, rv, m * u), _fma(m, u, (1.0 - m) * rv)]
+        rv, o = round_f32_with_margin(e_rv, ev)
+        ok &= o
+    return means, invstds, rm, rv, ok
+
+
+TILE_ROWS = (32, 64, 128, 256)    # the M-tile heights of the conv GEMMs' configurations
+
+
+def tile_stats_reference(y_ref, n, nseg, cout):
+    """(mean, invstd, running_mean, running_var) float32, bitwise what the conv epilogue's
+    statistics must be for the exact integer y_ref [nseg * n, cout, oh, ow] from fresh running
+    statistics (0, 1) -- or None where a per-tile shifted sum could reach 2^24."""
+    rows = rows_of(y_ref)
+    ys = rows.reshape(nseg, -1, cout)
+    cnt = ys.shape[1]
+    if not torch.equal(ys, ys.round()):
+        return None
+    # the per-tile sums are shifted by the tile's first row; whatever the tile height
+    for bm in TILE_ROWS:
+        for r0 in range(0, rows.shape[0], bm):
+            d = rows[r0:r0 + bm] - rows[r0]
+            if (d * d).sum(0).max().item() >= 2 ** 24:
+                return None
+    s1, s2 = ys.sum(1).long().tolist(), (ys * ys).sum(1).long().tolist()
+    cols = [stats_reference([s1[g][c] for g in range(nseg)], [s2[g][c] for g in range(nseg)], cnt,
+                            [0] * nseg, 0.0, 1.0, tile_form=True) for c in range(cout)]
+    assert all(col[4] for col in cols), "margin condition"
+    t32 = lambda v: torch.tensor(v, dtype=torch.float64).to(f32)
+    return (t32([[col[0][g] for col in cols] for g in range(nseg)]).reshape(-1),
+            t32([[col[1][g] for col in cols] for g in range(nseg)]).reshape(-1),
+            t32([col[2] for col in cols]), t32([col[3] for col in cols]))
+
+
+def check_bn_stats(y_ref, n, nseg, cout, mean, invstd, bn, exact=None):
+    """test_conv_fwd_bn_epilogue_stats's tolerances, against fp64 statistics of the exact y; and
+    bitwise against tile_stats_reference where it applies (exact=True: it must apply)."""
+    ref = tile_stats_reference(y_ref, n, nseg, cout)
+    assert ref is not None or not exact
+    if ref is not None:
+        same(mean, ref[0], "epilogue mean")
+        same(invstd, ref[1], "epilogue invstd")
+        same(bn.running_mean, ref[2], "epilogue running_mean")
+        same(bn.running_var, ref[3], "epilogue running_var")
     rm, rv = torch.zeros(cout, dtype=torch.float64), torch.ones(cout, dtype=torch.float64)
     for sg in range(nseg):
         ys = y_ref[sg * n:(sg + 1) * n]
@@ -682,7 +806,7 @@ def test_conv_fwd_bn_exact(cuda, dt, case):
                                                 bias=pr.bias.to(f32).to(cuda))
     torch.cuda.synchronize()
     same(y, rows_of(out.expect(dt)), "fwd_bn %s" % (case,))
-    check_bn_stats(out.ref, n, nseg, cout, mean, invstd, bn)
+    check_bn_stats(out.ref, n, nseg, cout, mean, invstd, bn, exact=True)
 
 
 @pytest.mark.parametrize("dt", [f32, bf])
@@ -698,7 +822,7 @@ def test_conv_fwd_bn_grouped_exact(cuda, dt):
     torch.cuda.synchronize()
     for g, (y, (mean, invstd)) in enumerate(res):
         same(y, rows_of(pr.outs[g].expect(dt)), "fwd_bn_grouped g%d" % g)
-        check_bn_stats(pr.outs[g].ref, n, nseg, cout, mean, invstd, bns[g])
+        check_bn_stats(pr.outs[g].ref, n, nseg, cout, mean, invstd, bns[g], exact=True)
 
 
 # ---- 7. dgrad fused with the BN + ReLU backward sums ------------------------------------------
