@@ -455,30 +455,10 @@ extern "C" size_t cn_conv_fwd_bn_workspace_floats(int dtype, int M, int Cout, in
   return (size_t)5 * mtiles_of(dtype, M, Cout, K) * Cout;
 }
 
-// Runs a forward conv GEMM (`a` of conv_fwd_args; `dtype`: what the dispatcher is given, DT_FP8 for
-// fp8 operands) with the train-mode BatchNorm statistics of the stored output in its epilogue
-// (st_mode 1: per-M-tile partials into ws), then reduces each problem's partials to mean / invstd
-// [nseg][Cout] and updates the running statistics, segment after segment.  G problems (a.grp
-// filled by the caller) or one: ws, mean, ... are arrays of G pointers.
-static int gemm_bn_stats(GemmArgs& a, int dtype, int la, int G, int nseg, float* const* ws,
-                         float* const* mean, float* const* invstd, float* const* run_mean,
-                         float* const* run_var, float momentum, float eps, hipStream_t st) {
-  const int bm = cn_gemm_bm(dtype, a.M, a.N, a.K, -1);
-  const long long mt = (a.M + bm - 1) / bm;
-  a.st_mode = 1;
-  a.st_ws = ws[0];
-  a.st_plane = mt * a.N;
-  a.st_seg_rows = a.M / nseg;
-  int rc = cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, G, st);
-  for (int g = 0; g < G && !rc; ++g)
-    rc = cn_bn_tile_stats_impl(ws[g], a.st_plane, (int)mt, bm, a.M, nseg, a.N, mean[g], invstd[g],
-                               run_mean[g], run_var[g], momentum, eps, st);
-  return rc;
-}
-
 // y = conv2d(x, w) + bias, and the train-mode BatchNorm statistics of y computed in the GEMM
-// epilogue (no separate pass over y): mean / invstd [nseg][Cout] of each of the nseg stacked
-// row segments (frames), running stats updated segment after segment.
+// epilogue (no separate pass over y; st_mode 1: per-M-tile partials of the stored output into
+// ws, then reduced): mean / invstd [nseg][Cout] of each of the nseg stacked row segments
+// (frames), running stats updated segment after segment.
 extern "C" int cn_conv_fwd_bn(int dtype, const void* x, long long ldx, int N, int H, int W, int Cin,
                               const void* w, int Cout, int KH, int KW, int stride, int pad, int dil,
                               const float* bias, void* y, long long ldy, int OH, int OW, int nseg,
@@ -490,64 +470,16 @@ extern "C" int cn_conv_fwd_bn(int dtype, const void* x, long long ldx, int N, in
                          ldy, OH, OW, a, la);
   if (rc) return rc;
   if (nseg < 1 || a.M % nseg || !ws) return CN_ERR_SHAPE;
-  return gemm_bn_stats(a, dtype, la, 1, nseg, &ws, &mean, &invstd, &run_mean, &run_var, momentum, eps,
-                       st);
-}
-
-// fp8 conv (cn_conv_fwd_fp8) with the BN statistics in its GEMM epilogue (cn_conv_fwd_bn's
-// reduction of the stored bf16 y), for configs[4]'s long-K narrow convs.  ws:
-// cn_conv_fwd_bn_workspace_floats(DT_FP8, M, Cout, K) floats.
-extern "C" int cn_conv_fwd_fp8_bn(const void* x8, long long ldx, int N, int H, int W, int Cin,
-                                  const void* w8, int Cout, int KH, int KW, int stride, int pad,
-                                  int dil, const float* bias, void* y, long long ldy, int OH, int OW,
-                                  const float* x_state, const float* w_state, int nseg, float* ws,
-                                  float* mean, float* invstd, float* run_mean, float* run_var,
-                                  float momentum, float eps, hipStream_t st) {
-  if (!fp8_operands_ok(Cin, ldx, x8, w8)) return CN_ERR_ALIGN;
-  GemmArgs a;
-  int la;
-  int rc = conv_fwd_args(DT_BF16, x8, ldx, N, H, W, Cin, w8, Cout, KH, KW, stride, pad, dil, bias, y,
-                         ldy, OH, OW, a, la);
+  const int bm = cn_gemm_bm(dtype, a.M, a.N, a.K, -1);
+  const long long mt = (a.M + bm - 1) / bm;
+  a.st_mode = 1;
+  a.st_ws = ws;
+  a.st_plane = mt * a.N;
+  a.st_seg_rows = a.M / nseg;
+  rc = cn_gemm_dispatch(a, dtype, 0, la, L_KC_DENSE, 1, st);
   if (rc) return rc;
-  if (nseg < 1 || a.M % nseg || !ws) return CN_ERR_SHAPE;
-  a.scale_a = x_state;
-  a.scale_b = w_state;
-  return gemm_bn_stats(a, DT_FP8, la, 1, nseg, &ws, &mean, &invstd, &run_mean, &run_var, momentum,
-                       eps, st);
-}
-
-// G stride-1 'same' convs of one input x and one shape that differ in dilation (pad = dil), bias
-// and weights -- the ASPP's atrous branches (deeplab/deeplabv3_encoder.py:22-31, :70-76) -- as ONE
-// grouped GEMM launch (blockIdx.z = branch) with the BN-statistics epilogue of cn_conv_fwd_bn per
-// branch.  The branches' launches are each one round of the chip whose time the tiles without
-// tap skipping set (§3.1); grouped, their tiles share the rounds.  w, bias, y, ws, mean, invstd,
-// run_mean, run_var, dil: host arrays of G entries (device pointers / ints); ws[g]:
-// cn_conv_fwd_bn_workspace_floats(dtype, M, Cout, K) floats each.  G <= 24.
-extern "C" int cn_conv_fwd_bn_grouped(int dtype, const void* x, long long ldx, int N, int H, int W,
-                                      int Cin, int G, const void* const* w, int Cout, int KH, int KW,
-                                      const int* dil, const float* const* bias, void* const* y,
-                                      long long ldy, int nseg, float* const* ws, float* const* mean,
-                                      float* const* invstd, float* const* run_mean,
-                                      float* const* run_var, float momentum, float eps, hipStream_t st) {
-  if (G < 1 || G > GEMM_MAXG || KH != KW || KH % 2 == 0) return CN_ERR_SHAPE;
-  GemmArgs a;
-  int la;
-  const int d0 = dil[0], p0 = d0 * (KH / 2);
-  int rc = conv_fwd_args(dtype, x, ldx, N, H, W, Cin, w[0], Cout, KH, KW, 1, p0, d0, bias[0], y[0],
-                         ldy, H, W, a, la);
-  if (rc) return rc;
-  if (la != L_KC_CONV || nseg < 1 || a.M % nseg) return CN_ERR_SHAPE;
-  a.ngroup = G;
-  for (int g = 0; g < G; ++g) {
-    if (dil[g] < 1 || !ws[g]) return CN_ERR_SHAPE;
-    a.grp.A[g] = x;
-    a.grp.B[g] = w[g];
-    a.grp.C[g] = y[g];
-    a.grp.bias[g] = bias[g];
-    a.grp.ST[g] = ws[g];
-    a.grp.dil[g] = dil[g];
-  }
-  return gemm_bn_stats(a, dtype, la, G, nseg, ws, mean, invstd, run_mean, run_var, momentum, eps, st);
+  return cn_bn_tile_stats_impl(ws, a.st_plane, (int)mt, bm, a.M, nseg, a.N, mean, invstd, run_mean,
+                               run_var, momentum, eps, st);
 }
 
 extern "C" size_t cn_conv_dgrad_bn_workspace_floats(int dtype, int M, int Cin, int K) {

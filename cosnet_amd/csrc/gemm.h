@@ -32,12 +32,6 @@ struct GemmGroup {
   // fp8 operands: per-problem dequantisation scales (null: the launch-wide scale_a / scale_b)
   const float* SA[GEMM_MAXG];
   const float* SB[GEMM_MAXG];
-  // grouped convs that differ in more than their operands (round 6, the ASPP's atrous branches):
-  // per-problem bias, BN-statistics workspace (EPI 1) and dilation of the A gather (> 0: the
-  // gather's offset / step become -dil / +dil, 'same' padding); null / 0: the launch-wide ones
-  const float* bias[GEMM_MAXG];
-  float* ST[GEMM_MAXG];
-  int dil[GEMM_MAXG];
 };
 
 struct GemmArgs {
@@ -59,7 +53,8 @@ struct GemmArgs {
   const float* scale_a;        // fp8 operands: device per-tensor dequantisation scales (C *= sa * sb)
   const float* scale_b;
   int cfg;                     // tile configuration (gemm.hip kCfg), -1 = shape heuristic
-  // BatchNorm epilogues (batch == 1, nsplit == 1, row_map == 0, c_mode 0 only):
+  // BatchNorm epilogues (st_mode != 0: one problem -- batch == 1, never a grouped launch --
+  // nsplit == 1, row_map == 0, c_mode 0 only):
   //  st_mode 1: per-(M-tile, column) statistics of the STORED C for train-mode BN: planes
   //             [K, sum(c-K), sum((c-K)^2)] for the tile's first segment (rows < the next
   //             multiple of st_seg_rows) and [sum, sumsq] for the second, K = the tile's first
@@ -67,8 +62,8 @@ struct GemmArgs {
   //  st_mode 2: BN backward reduce of the stored C (= dy of a BN + ReLU whose pre-BN input is
   //             br_x): dz = dy * (br_x * k1 + sf > 0), xh = (br_x - mu) * is;
   //             planes [sum dz, sum dz * xh].  k1 = gamma * is, sf = beta - mu * k1.
-  //  st_mode 4: eval-mode BN folded into a forward conv (cn_conv_fwd_affine; no statistics, no
-  //             grouped launch): C = act(fma(acc + bias, br_gamma[n], br_beta[n]) + br_x[m][n]),
+  //  st_mode 4: eval-mode BN folded into a forward conv (cn_conv_fwd_affine; no statistics):
+  //             C = act(fma(acc + bias, br_gamma[n], br_beta[n]) + br_x[m][n]),
   //             br_gamma / br_beta = the folded scale / shift, br_x / br_ldx = the residual rows
   //             (C's type, nullable), act / prelu below.  With e4m3 operands (bf16 C;
   //             cn_conv_fwd_fp8_affine) the same fp32 value t is also written as its saturating
@@ -80,7 +75,8 @@ struct GemmArgs {
   int st_seg_rows;
   const void* br_x; long long br_ldx;
   const float* br_mean; const float* br_invstd; const float* br_gamma; const float* br_beta;
-  int ngroup;                  // > 0: grouped launch (GemmGroup), batch = ngroup, nsplit 1
+  int ngroup;                  // > 0: grouped launch (GemmGroup), batch = ngroup, nsplit 1,
+                               // st_mode 0; the problems differ in their operands only
   GemmGroup grp;
   int wt;                      // C stores: 4 non-temporal, 0 plain (other: write-through, sc1);
                                // set by cn_gemm_dispatch
@@ -91,7 +87,7 @@ struct GemmArgs {
   unsigned char* c8; long long ldc8;
   const float* q_state;
   // st_mode 5: st_mode 4 with an fp32 addend in front of the affine instead of the residual behind
-  //            it (cn_conv_fwd_affine_add; bf16 / fp32 operands, no grouped launch):
+  //            it (cn_conv_fwd_affine_add; bf16 / fp32 operands):
   //            C = act(fma(acc + bias + add[f * add_rows + r][n], br_gamma[n], br_beta[n])) for
   //            row m = j * add_rows + r, f = add_map ? add_map[j] : j.  add: fp32 rows add_ld floats
   //            apart (64-bit row addressing); add_map: device int32, one entry per block of

@@ -471,16 +471,10 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
   const int batch = bz / p.nsplit, split = bz - batch * p.nsplit;
   int kbeg = split * p.k_chunk;
   int kend = min(p.K, kbeg + p.k_chunk);
-  // the A gather's geometry: per problem in a grouped launch of convs of different dilations
-  ConvGeom gA = p.ga;
-  if constexpr (LA == L_KC_CONV) {
-    if (p.ngroup && p.grp.dil[batch] > 0) {
-      const int dl = p.grp.dil[batch];
-      gA.off_y = gA.off_x = -dl;
-      gA.step_y = gA.step_x = dl;
-    }
-  }
-  const float* bias = (p.ngroup && p.grp.bias[batch]) ? p.grp.bias[batch] : p.bias;
+  // (named once here: with p.ga / p.bias written out at each use eleven bf16 tiles allocate 2-8
+  // VGPRs differently, profiles/r14_retired_grouped_fp8_stats_ab.txt)
+  const ConvGeom& gA = p.ga;
+  const float* bias = p.bias;
   if constexpr (LA == L_KC_CONV) {
     // Vertical tap skipping (conv forward / stride-1 dgrad gathers; k = (r, s, ci), r-major): the
     // taps r whose source rows y = oy st + off_y + r step_y miss the image for EVERY row of this
@@ -1116,7 +1110,7 @@ __global__ __launch_bounds__(WM * WN * 64, (EPI && (sizeof(T) == 2 || (sizeof(T)
       }
     }
     __syncthreads();
-    float* ws = ((p.ngroup && p.grp.ST[batch]) ? p.grp.ST[batch] : p.st_ws) + (long long)tm * p.N;
+    float* ws = p.st_ws + (long long)tm * p.N;
     for (int t = tid; t < nq * BN; t += NT) {
       const int q = t / BN, c = t % BN;
       float a = 0.f;
@@ -1327,12 +1321,6 @@ static int launch_f8(const GemmArgs& a, int batch, hipStream_t st) {
   // (the 256x256 tile would spill its fp8 fragments: 128x128 serves the wide products too)
   const int c = pick_cfg(a, batch);
   if constexpr (sizeof(CT) == 2 && std::is_same<T8, f8e4m3>::value) {
-    // fp8 conv forward with the BN-statistics epilogue (round 6; the bf16 path's EPI 1)
-    if (a.st_mode == 1) {
-      if (c == 12) return launch_c<T8, CT, 12, LA, L_KC_DENSE, 1>(a, batch, st);
-      if (c == 13) return launch_c<T8, CT, 13, LA, L_KC_DENSE, 1>(a, batch, st);
-      return launch_c<T8, CT, 11, LA, L_KC_DENSE, 1>(a, batch, st);
-    }
     // fp8 conv forward with the eval-mode BN fold (cn_conv_fwd_fp8_affine; the bf16 path's EPI 4)
     if (a.st_mode == 4) {
       if (c == 12) return launch_c<T8, CT, 12, LA, L_KC_DENSE, 4>(a, batch, st);
@@ -1406,16 +1394,17 @@ int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb,
   // pointer loader
   if (la == L_KC_CONV && (a.ga.C % bk != 0 || !buf_ok(L_KC_CONV, a, true, esz))) la = L_KC_CONV_G;
   if (!buf_ok(la, a, true, esz) || !buf_ok(lb, a, false, esz)) return CN_ERR_SHAPE;
+  // a BN epilogue (st_mode, gemm.h) serves one problem: no batch, no grouped launch
+  if (a.st_mode && (batch != 1 || a.ngroup)) return CN_ERR_UNSUPPORTED;
   if (ws_eligible(a, dtype, c_f32, la, lb, batch)) {
     ++g_ws_launches;
     return cn_gemm_ws_launch(a, g_ws_mode == 3 ? 1 : 0, st);
   }
   if (dtype == DT_FP8) {
     if (lb != L_KC_DENSE || a.nsplit != 1) return CN_ERR_UNSUPPORTED;
-    if (a.st_mode && ((a.st_mode != 1 && a.st_mode != 4) || batch != 1 || a.row_map || a.c_mode || c_f32))
-      return CN_ERR_UNSUPPORTED;
+    if (a.st_mode && (a.st_mode != 4 || a.row_map || a.c_mode || c_f32)) return CN_ERR_UNSUPPORTED;
     if (a.st_mode == 4) {   // the eval-mode BN fold: bf16 C and / or the e4m3 image
-      if (a.ngroup || !a.br_gamma || !a.br_beta || a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu) ||
+      if (!a.br_gamma || !a.br_beta || a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu) ||
           (!a.C && !a.c8) || (a.c8 && !a.q_state))
         return CN_ERR_UNSUPPORTED;
       // a forced configuration that has no folded epilogue is refused, not replaced
@@ -1441,18 +1430,17 @@ int cn_gemm_dispatch(const GemmArgs& a_in, int dtype, int c_f32, int la, int lb,
     return CN_ERR_UNSUPPORTED;
   }
   if (a.st_mode) {
-    // grouped (EPI 1 only): one problem per blockIdx.z, each with its own statistics workspace
-    if ((batch != 1 && !(a.ngroup == batch && a.st_mode == 1)) || a.nsplit != 1 || a.row_map || a.c_mode ||
-        lb != L_KC_DENSE || (la != L_KC_DENSE && la != L_KC_CONV && la != L_KC_CONV_G))
+    if (a.nsplit != 1 || a.row_map || a.c_mode || lb != L_KC_DENSE ||
+        (la != L_KC_DENSE && la != L_KC_CONV && la != L_KC_CONV_G))
       return CN_ERR_UNSUPPORTED;
-    if (a.st_mode == 4 && (a.ngroup || c_f32 != (dtype == DT_F32) || !a.br_gamma || !a.br_beta ||
+    if (a.st_mode == 4 && (c_f32 != (dtype == DT_F32) || !a.br_gamma || !a.br_beta ||
                            a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu)))
       return CN_ERR_UNSUPPORTED;
     if (a.st_mode < 1 || a.st_mode == 3 || a.st_mode > 5) return CN_ERR_UNSUPPORTED;
     if (a.st_mode == 5) {
       // the addend epilogue: the plain product and the one-tap-per-K-tile conv gather only (the
       // per-thread-pointer gather is not instantiated: refused, not replaced)
-      if (a.ngroup || c_f32 != (dtype == DT_F32) || !a.br_gamma || !a.br_beta || !a.add || a.add_rows <= 0 ||
+      if (c_f32 != (dtype == DT_F32) || !a.br_gamma || !a.br_beta || !a.add || a.add_rows <= 0 ||
           a.M % a.add_rows || a.act < 0 || a.act > 2 || (a.act == 2 && !a.prelu) || la == L_KC_CONV_G)
         return CN_ERR_UNSUPPORTED;
       if (dtype == DT_BF16)

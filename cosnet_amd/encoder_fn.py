@@ -16,13 +16,12 @@ The forward saves one named record per module (StemRec, BlockRec, AsppRec), read
 the backwards, fp8_infer.py's calibration walk and the tests.  The walks over an encoder here, in
 fp8_infer.py and in tools/ take its structure from layers / blocks / layer_of / aspp_branches.
 
-Two forward variants were measured and not adopted (profiles/r06_aspp_grouped_fp8_stats_ab.txt);
-their switches were removed afterwards, source at commit c31c537, the kernels and their ops
-wrappers stay: the ASPP's three atrous convs as one grouped launch (cn_conv_fwd_bn_grouped,
-CN_ASPP_GROUPED: level with the three launches in the two-stream step, where the depth stream
-already fills the CUs a one-round launch leaves idle), and the BN statistics of the long-K narrow
-fp8 convs from the fp8 GEMM's epilogue (cn_conv_fwd_fp8_bn, CN_FP8_FUSE_STATS: 0.8 % slower on
-the configs[4] step, the fp8 tiles' epilogue being long next to their K loop).
+Two forward variants were measured, not adopted and retired with their kernels, entry points
+and ops wrappers (profiles/r06_aspp_grouped_fp8_stats_ab.txt; the source is in commit 142913f and
+before): the ASPP's three atrous convs as one grouped launch (level with the three launches in
+the two-stream step, where the depth stream already fills the CUs a one-round launch leaves
+idle), and the BN statistics of the long-K narrow fp8 convs from the fp8 GEMM's epilogue (0.8 %
+slower on the configs[4] step, the fp8 tiles' epilogue being long next to their K loop).
 """
 import collections
 import os

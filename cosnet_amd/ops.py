@@ -241,10 +241,10 @@ def _fwd_conv(x, n, h, w, wf, cout, k, stride, pad, dil, bias, out, out_dtype):
              out.data_ptr(), ld(out), oh, ow))
 
 
-def _fwd_record(tag, g, es_in, es_out, G=1):
-    """G forward convs of one input: x and the weights read, y written once."""
-    return (G * 2.0 * g.M * g.cout * g.K, (tag, g.M, g.cout * G, g.K),
-            es_in * (g.n * g.h * g.w * g.cin + G * g.cout * g.K) + es_out * G * g.M * g.cout)
+def _fwd_record(tag, g, es_in, es_out):
+    """A forward conv: x and the weights read, y written once."""
+    return (2.0 * g.M * g.cout * g.K, (tag, g.M, g.cout, g.K),
+            es_in * (g.n * g.h * g.w * g.cin + g.cout * g.K) + es_out * g.M * g.cout)
 
 
 def _dgrad_conv(dy, n, oh, ow, wt, cin, k, spd, out, h, w, out_dtype):
@@ -419,24 +419,6 @@ def fwd_split_floats(x, m, cout, kdim):
     return int(nv.query("cn_conv_fwd_workspace_floats", dtc(x), m, cout, kdim))
 
 
-def _conv_fwd_bn_launch(name, head, dev, ws_dtype, g, bns, nseg, prof, arrays=False):
-    """Launches a conv + BN-statistics entry point: `head`, then the statistics tail all of them
-    share -- nseg, workspace, mean, invstd, running mean and variance (one set per BN of `bns`;
-    arrays=True: each as a host array of pointers), momentum, eps -- and counts the batches.
-    prof: the arguments of _fwd_record around g.  Returns [(mean, invstd)] per BN."""
-    nws = int(nv.query("cn_conv_fwd_bn_workspace_floats", ws_dtype, g.M, g.cout, g.K))
-    sets = []
-    for bn in bns:
-        mean = torch.empty((nseg * g.cout,), dtype=torch.float32, device=dev)
-        sets.append((_workspace(dev, nws)[0], mean, torch.empty_like(mean), bn.running_mean, bn.running_var))
-    tail = [_ptrs(col) if arrays else nv.ptr(col[0]) for col in zip(*sets)]
-    with _profiled(_fwd_record, prof[0], g, *prof[1:]):
-        nv.call(name, *head, nseg, *tail, _momentum(bns[0]), float(bns[0].eps), nv.stream())
-    for bn in bns:
-        _count_batches(bn, nseg)
-    return [(s[1], s[2]) for s in sets]
-
-
 def conv_fwd_bn(x, n, h, w, wf, cout, k, stride, pad, dil, bn, nseg=1, bias=None):
     """Train mode: y = conv(x) (+ bias) and the BN batch statistics of y from the GEMM epilogue
     (cn_conv_fwd_bn: no pass of its own over y).  Returns (y, oh, ow, (mean, invstd)) with
@@ -447,10 +429,15 @@ def conv_fwd_bn(x, n, h, w, wf, cout, k, stride, pad, dil, bn, nseg=1, bias=None
         # split over K: the statistics come from their own pass over the reduced output
         conv_fwd(x, n, h, w, wf, cout, k, stride, pad, dil, bias=bias, out=out)
         return out, g.oh, g.ow, bn_stats(out, bn, True, nseg)
-    es = x.element_size()
-    stats, = _conv_fwd_bn_launch("cn_conv_fwd_bn", (dtc(x), *args), x.device, dtc(x), g, [bn], nseg,
-                                 ("fwd", es, es))
-    return out, g.oh, g.ow, stats
+    nws = int(nv.query("cn_conv_fwd_bn_workspace_floats", dtc(x), g.M, cout, g.K))
+    ws = _workspace(x.device, nws)[0]
+    mean = torch.empty((nseg * cout,), dtype=torch.float32, device=x.device)
+    invstd = torch.empty_like(mean)
+    with _profiled(_fwd_record, "fwd", g, x.element_size(), x.element_size()):
+        nv.call("cn_conv_fwd_bn", dtc(x), *args, nseg, nv.ptr(ws), mean.data_ptr(), invstd.data_ptr(),
+                nv.ptr(bn.running_mean), nv.ptr(bn.running_var), _momentum(bn), float(bn.eps), nv.stream())
+    _count_batches(bn, nseg)
+    return out, g.oh, g.ow, (mean, invstd)
 
 
 def conv_dgrad_bn(dy, n, oh, ow, wt, cin, k, pad, dil, x, stats, bn, dgamma=None, dbeta=None):
@@ -585,35 +572,6 @@ def conv_fwd_fp8_affine(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_
                 shift.data_ptr(), *_mat(res, 0), int(act), nv.ptr(prelu), *_mat(out, 0), *_mat(out8, 0),
                 nv.ptr(out_state), oh, ow, nv.stream())
     return out, out8, oh, ow
-
-
-def conv_fwd_bn_grouped(x, n, h, w, wfs, cout, k, dils, bns, nseg=1, biases=None):
-    """The ASPP's atrous branches as ONE grouped launch (cn_conv_fwd_bn_grouped): for each g,
-    y_g = conv(x, wfs[g], dilation dils[g], padding dils[g]) (+ biases[g]) and the BN batch
-    statistics of y_g from the GEMM epilogue (as conv_fwd_bn).  Returns [(y_g, (mean, invstd))]."""
-    G = len(wfs)
-    cin = wfs[0].shape[1] // (k * k)
-    g = _Conv(n, h, w, cin, h, w, cout, k, n * h * w, k * k * cin)   # 'same' convs: oh, ow = h, w
-    _check_train_rows(g.M, nseg, cout)
-    ys = [torch.empty((g.M, cout), dtype=x.dtype, device=x.device) for _ in range(G)]
-    es = x.element_size()
-    stats = _conv_fwd_bn_launch(
-        "cn_conv_fwd_bn_grouped",
-        (dtc(x), *_mat(x), n, h, w, g.cin, G, _ptrs(wfs), cout, k, k, (ctypes.c_int * G)(*dils),
-         _ptrs(biases or [None] * G), _ptrs(ys), cout),
-        x.device, dtc(x), g, bns, nseg, ("fwd", es, es, G), arrays=True)
-    return list(zip(ys, stats))
-
-
-def conv_fwd_fp8_bn(x8, n, h, w, wf8, cout, k, stride, pad, dil, x_state, w_state, bn, nseg=1,
-                    bias=None):
-    """conv_fwd_fp8 + the BN batch statistics of its stored bf16 output from the GEMM epilogue
-    (cn_conv_fwd_fp8_bn), as conv_fwd_bn does for bf16.  Returns (y, oh, ow, (mean, invstd))."""
-    g, out, args = _fwd_conv(x8, n, h, w, wf8, cout, k, stride, pad, dil, bias, None, torch.bfloat16)
-    _check_train_rows(g.M, nseg, cout)
-    stats, = _conv_fwd_bn_launch("cn_conv_fwd_fp8_bn", (*args, x_state.data_ptr(), w_state.data_ptr()),
-                                 x8.device, 2, g, [bn], nseg, ("fwd8", 1, 2))   # workspace query: dtype 2 = fp8
-    return out, g.oh, g.ow, stats
 
 
 def conv_dgrad(dy, n, oh, ow, wt, cin, k, stride, pad, dil, h, w, out=None, accumulate=False):

@@ -37,7 +37,7 @@ def test_head_header_parses_and_the_other_sets_are_unchanged():
     assert args[19:] == [P, P, P, L, P, I, I, P, P]
     assert sigs["cn_conv_fwd_partial"] == base          # cn_conv_fwd's operands, stream included
     core = _native.exported_symbols()
-    assert len(core) == 96 and not set(core) & set(HEAD)
+    assert len(core) == 94 and not set(core) & set(HEAD)
     assert _native.extension_symbols() == ["cn_bn_fold_table", "cn_conv_fwd_affine"]
     assert _native.fp8_extension_symbols() == ["cn_conv_fwd_fp8_affine"]
     for n in HEAD:

@@ -42,16 +42,21 @@ def test_pinned_signatures(sigs):
                                   ["dtype", "x", "ld", "N", "HW", "C", "scale", "y", "ws", "stream"])
     assert sigs["cn_gemm_ws_launches"] == (S, [], [])                      # (void)
     assert sigs["cn_build_source_hash"] == (ctypes.c_char_p, [], [])
-    # `const int* dil` and `float* const* ws` are both pointers
-    res, args, names = sigs["cn_conv_fwd_bn_grouped"]
-    assert len(args) == 25
-    assert args[names.index("dil")] is P and args[names.index("ws")] is P and args[names.index("w")] is P
-    assert [t for t in args if t is F] == [F, F] and names[-3:] == ["momentum", "eps", "stream"]
+    # `float* const* dws`, `const float* const* x_states` and `const int* ia` are all pointers
+    res, args, names = sigs["cn_conv_wgrad_fp8"]
+    assert len(args) == 23
+    assert [n for n, t in zip(names, args) if t is P] == ["xs8", "dys8", "dws", "x_states", "dy_states", "ws",
+                                                          "stream"]
+    assert not [t for t in args if t is F] and names[-3:] == ["ws", "ws_floats", "stream"]
+    res, args, names = sigs["cn_coatt_fused_fwd_idx"]
+    assert len(args) == 17
+    assert [n for n, t in zip(names, args) if t is P] == ["vat", "va", "vb", "ia", "ib", "za", "zb", "ws", "stream"]
+    assert names[-3:] == ["ws", "ws_bytes", "stream"]
 
 
 def test_parse_finds_every_declared_entry_point(header, sigs):
     names = set(re.findall(r"^(?:int|size_t|const char\*)\s+(cn_\w+)\(", header, re.M))
-    assert len(names) == 96
+    assert len(names) == 94
     assert set(sigs) == names == set(_native.exported_symbols())
     assert all(len(args) == len(pnames) for _, args, pnames in sigs.values())
 

@@ -129,21 +129,6 @@ def test_fwd_bn_needs_its_workspace(t):
     refused(SHAPE, "cn_conv_fwd_bn", *fwd(t.a, t.a, t.a, dt=BF), *bn_tail(t, ws=False))
 
 
-def fwd_bn_grouped(t, g, k):
-    a, f = t.a.data_ptr(), t.f.data_ptr()
-    dil = (ctypes.c_int * g)(*[1] * g)
-    return (BF, a, 16, N, H, W, 16, g, arr(g, a), 16, k, k, dil, arr(g, None), arr(g, a), 16, 1,
-            arr(g, f), arr(g, f), arr(g, f), arr(g, f), arr(g, f), 0.1, 1e-5)
-
-
-def test_fwd_bn_grouped_too_many_branches(t):
-    refused(SHAPE, "cn_conv_fwd_bn_grouped", *fwd_bn_grouped(t, 25, 3))
-
-
-def test_fwd_bn_grouped_even_kernel(t):
-    refused(SHAPE, "cn_conv_fwd_bn_grouped", *fwd_bn_grouped(t, 2, 2))
-
-
 def test_dgrad_bn_needs_its_workspace(t):
     a, f = t.a.data_ptr(), t.f.data_ptr()
     refused(SHAPE, "cn_conv_dgrad_bn", BF, a, 16, N, H, W, 16, a, 16, 1, 1, 0, 1, a, 16, H, W, a, 16, f,

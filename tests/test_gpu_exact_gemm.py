@@ -69,7 +69,6 @@ WS_CASE = (3, 128, 17, 19, 328, 1, 1, 0, 1)
 WS_CASE_T = (3, 328, 17, 19, 128, 1, 1, 0, 1)   # its transpose: the dgrad's K = 128 is eligible
 # n per segment, cin, h, w, cout, k, stride, pad, dil, nseg
 BN_CASES = [(2, 64, 13, 11, 64, 3, 1, 2, 2, 2), (1, 256, 30, 20, 256, 1, 1, 0, 1, 2)]
-BN_GROUPED_CASE = (2, 64, 13, 11, 64, (1, 2, 5), 2)   # n per segment, cin, h, w, cout, dils, nseg
 # n, cin, h, w, cout, k, pad, dil (test_conv_dgrad_bn_epilogue_reduce's layout)
 DGRAD_BN_CASES = [(2, 64, 13, 11, 64, 3, 2, 2), (1, 128, 9, 9, 256, 1, 0, 1)]
 FP8_FWD_CASES = [(2, 64, 13, 11, 128, 1, 1, 0, 1), (2, 32, 15, 9, 64, 3, 1, 2, 2),
@@ -210,20 +209,6 @@ def gemm_problem(b, m, n, k, seed=0, kb_lim=None):
     return pr
 
 
-@functools.lru_cache(maxsize=None)
-def bn_grouped_problem(case):
-    n, cin, h, w, cout, dils, nseg = case
-    x = ints((nseg * n, cin, h, w), -2, 2, 301)
-    pr = SimpleNamespace(x=x, ws=[], biases=[], outs=[])
-    for g, dl in enumerate(dils):
-        wt = ints((cout, cin, 3, 3), -2, 2, 310 + g)
-        bias = ints((cout,), -2, 2, 320 + g)
-        pr.ws.append(wt)
-        pr.biases.append(bias)
-        pr.outs.append(Out(F.conv2d(x, wt, bias, 1, dl, dl), bound_of(9 * cin, x, wt, bias), repr_=True))
-    return pr
-
-
 BN_MEAN, BN_INVSTD, BN_BETA = 2.0, 0.5, 0.25
 
 
@@ -339,7 +324,6 @@ def all_problems():
     for case in BN_CASES:
         n, cin, h, w, cout, k, s, p, d, nseg = case
         res += named("fwd-bn %s" % (case,), {"fwd": conv_problem((nseg * n,) + case[1:9], REPR, 3, False).outs["fwd"]})
-    res += named("fwd-bn-grouped", bn_grouped_problem(BN_GROUPED_CASE).outs)
     for case in DGRAD_BN_CASES:
         res += named("dgrad-bn %s" % (case,), dgrad_bn_problem(case).outs)
     for case in FP8_FWD_CASES:
@@ -809,22 +793,6 @@ def test_conv_fwd_bn_exact(cuda, dt, case):
     check_bn_stats(out.ref, n, nseg, cout, mean, invstd, bn, exact=True)
 
 
-@pytest.mark.parametrize("dt", [f32, bf])
-def test_conv_fwd_bn_grouped_exact(cuda, dt):
-    n, cin, h, w, cout, dils, nseg = BN_GROUPED_CASE
-    pr = bn_grouped_problem(BN_GROUPED_CASE)
-    for o in pr.outs:
-        verify(o)
-    bns = [K._BN(cout, cuda, 70 + g) for g in range(len(dils))]
-    res = ops.conv_fwd_bn_grouped(operand(rows_of(pr.x), dt, cuda), nseg * n, h, w,
-                                  [wf_of(wt, dt, cuda) for wt in pr.ws], cout, 3, list(dils), bns, nseg,
-                                  biases=[b.to(f32).to(cuda) for b in pr.biases])
-    torch.cuda.synchronize()
-    for g, (y, (mean, invstd)) in enumerate(res):
-        same(y, rows_of(pr.outs[g].expect(dt)), "fwd_bn_grouped g%d" % g)
-        check_bn_stats(pr.outs[g].ref, n, nseg, cout, mean, invstd, bns[g], exact=True)
-
-
 # ---- 7. dgrad fused with the BN + ReLU backward sums ------------------------------------------
 @pytest.mark.parametrize("dt", [f32, bf])
 @pytest.mark.parametrize("case", DGRAD_BN_CASES)
@@ -857,8 +825,8 @@ E4M3, E5M2 = torch.float8_e4m3fn, torch.float8_e5m2
 
 @pytest.mark.parametrize("case", FP8_FWD_CASES)
 def test_conv_fwd_fp8_exact(cuda, case):
-    """cn_conv_fwd_fp8 (bias) and cn_conv_fwd_fp8_bn: y = one rounding of acc * sx * sw + bias (a
-    scale applied after the rounding would miss the ties); the statistics as in 6, of the stored y."""
+    """cn_conv_fwd_fp8 (bias): y = one rounding of acc * sx * sw + bias (a scale applied after the
+    rounding would miss the ties)."""
     n, cin, h, w, cout, k, s, p, d = case
     pr = fp8_fwd_problem(case)
     out = pr.outs["fwd"]
@@ -870,14 +838,10 @@ def test_conv_fwd_fp8_exact(cuda, case):
     m = n * pr.oh * pr.ow
     ybuf, yv = output(m, cout, bf, cuda)
     ops.conv_fwd_fp8(x8, n, h, w, w8, cout, k, s, p, d, xs, ws, bias=bias, out=yv)
-    bn = K._BN(cout, cuda, 44)
-    yb, _, _, (mean, invstd) = ops.conv_fwd_fp8_bn(x8, n, h, w, w8, cout, k, s, p, d, xs, ws, bn, 1, bias=bias)
     torch.cuda.synchronize()
     want = rows_of(out.expect(bf))
     same(yv, want, "fwd_fp8 %s" % (case,))
     untouched(ybuf, m, cout, "fwd_fp8")
-    same(yb, want, "fwd_fp8_bn %s" % (case,))
-    check_bn_stats(K.nchw(want, n, pr.oh, pr.ow).double(), n, 1, cout, mean, invstd, bn)
     # bias-free, every e4m3 mantissa bit in use: most outputs are inexact in bf16 (multiples of 1/8)
     full = pr.outs["fwd_full"]
     verify(full)

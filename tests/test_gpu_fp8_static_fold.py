@@ -147,7 +147,7 @@ def test_one_launch_per_conv_bn_pair(cuda, folded, monkeypatch):
         monkeypatch.setattr(ops, name, f)
 
     for name in ("conv_fwd_fp8_affine", "conv_fwd_affine", "conv_fwd_fp8", "conv_fwd", "bn_stats", "bn_apply",
-                 "bn_apply_q8", "conv_fwd_fp8_bn", "conv_fwd_bn"):
+                 "bn_apply_q8", "conv_fwd_bn"):
         wrap(name)
     with torch.no_grad():
         m._set_dtype()

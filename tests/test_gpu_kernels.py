@@ -777,72 +777,6 @@ def test_conv_fwd_fp8(cuda, case):
     assert err <= 1e-2, err
 
 
-@pytest.mark.parametrize("case", [(2, 64, 13, 11, 128, 1, 1, 0, 1, 2), (2, 256, 17, 15, 256, 3, 1, 2, 2, 2),
-                                  (1, 128, 30, 30, 512, 3, 1, 6, 6, 1), (2, 512, 9, 9, 64, 1, 1, 0, 1, 2)])
-def test_conv_fwd_fp8_bn_epilogue_stats(cuda, case):
-    """cn_conv_fwd_fp8_bn (configs[4]): the fp8 conv's output equals cn_conv_fwd_fp8's BITWISE
-    (same kernel, EPI 1 only adds the reduction), and the per-segment batch statistics come out of
-    the epilogue equal to fp64 statistics of that stored output (running stats in segment order)."""
-    n, cin, h, w, cout, k, s, p, d, nseg = case
-    x = rnd((nseg * n, cin, h, w), torch.float32, 41, scale=2.0) + 1.0
-    wt = rnd((cout, cin, k, k), torch.float32, 42, scale=(2.0 / (cin * k * k)) ** 0.5)
-    xs, ws = ops.fp8_state(cuda), ops.fp8_state(cuda)
-    x8 = ops.fp8_quant(nhwc(x).float().to(cuda).contiguous(), xs, ops.FP8_CURRENT)
-    w8 = ops.fp8_quant(wt.permute(0, 2, 3, 1).reshape(cout * k * k, cin).float().to(cuda).contiguous(),
-                       ws, ops.FP8_CURRENT).view(cout, k * k * cin)
-    bias = rnd((cout,), torch.float32, 43, scale=0.5).float().to(cuda)
-    bn = _BN(cout, cuda, 44)
-    y0, oh, ow = ops.conv_fwd_fp8(x8, nseg * n, h, w, w8, cout, k, s, p, d, xs, ws, bias=bias)
-    y, oh, ow, (mean, invstd) = ops.conv_fwd_fp8_bn(x8, nseg * n, h, w, w8, cout, k, s, p, d, xs, ws,
-                                                    bn, nseg, bias=bias)
-    torch.cuda.synchronize()
-    assert torch.equal(y, y0)
-    yr = nchw(y, nseg * n, oh, ow).double().cpu()
-    rm, rv = torch.zeros(cout, dtype=torch.float64), torch.ones(cout, dtype=torch.float64)
-    for sg in range(nseg):
-        ys = yr[sg * n:(sg + 1) * n]
-        mu = ys.mean(dim=(0, 2, 3))
-        var = ys.var(dim=(0, 2, 3), unbiased=False)
-        cnt = ys.numel() // cout
-        assert torch.allclose(mean[sg * cout:(sg + 1) * cout].double().cpu(), mu, atol=1e-4 * (1 + mu.abs().max().item()), rtol=1e-5)
-        assert torch.allclose(invstd[sg * cout:(sg + 1) * cout].double().cpu(), 1 / torch.sqrt(var + 1e-5), rtol=1e-4)
-        rm = 0.9 * rm + 0.1 * mu
-        rv = 0.9 * rv + 0.1 * var * cnt / (cnt - 1)
-    assert torch.allclose(bn.running_mean.double().cpu(), rm, rtol=1e-4, atol=1e-5)
-    assert torch.allclose(bn.running_var.double().cpu(), rv, rtol=1e-4, atol=1e-5)
-
-
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("case", [(2, 256, 17, 15, 128, (1, 2, 5), 2), (1, 512, 30, 30, 512, (6, 12, 18), 1)])
-def test_conv_fwd_bn_grouped_is_the_separate_launches(cuda, dt, case):
-    """cn_conv_fwd_bn_grouped (the ASPP's atrous branches in one launch: per-problem weights,
-    bias, dilation and statistics workspace) is BITWISE the G separate cn_conv_fwd_bn launches --
-    outputs, batch statistics and running-stat updates -- and those are pinned to fp64 by
-    test_conv_fwd_bn_epilogue_stats."""
-    n, cin, h, w, cout, dils, nseg = case
-    G = len(dils)
-    x = rnd((nseg * n, cin, h, w), dt, 51, scale=2.0) + 1.0
-    xg = nhwc(x).to(dt).to(cuda).contiguous()
-    wfs, biases = [], []
-    for g in range(G):
-        wt = rnd((cout, cin, 3, 3), dt, 52 + g, scale=(2.0 / (cin * 9)) ** 0.5)
-        wfs.append(wt.permute(0, 2, 3, 1).reshape(cout, 9 * cin).to(dt).to(cuda).contiguous())
-        biases.append(rnd((cout,), torch.float32, 60 + g, scale=0.5).float().to(cuda))
-    bns_a = [_BN(cout, cuda, 70 + g) for g in range(G)]
-    bns_b = [_BN(cout, cuda, 70 + g) for g in range(G)]
-    outs = ops.conv_fwd_bn_grouped(xg, nseg * n, h, w, wfs, cout, 3, list(dils), bns_a, nseg, biases=biases)
-    refs = [ops.conv_fwd_bn(xg, nseg * n, h, w, wfs[g], cout, 3, 1, dils[g], dils[g], bns_b[g], nseg,
-                            bias=biases[g]) for g in range(G)]
-    torch.cuda.synchronize()
-    for g in range(G):
-        y, (m, i) = outs[g]
-        yr, _, _, (mr, ir) = refs[g]
-        assert torch.equal(y, yr), g
-        assert torch.equal(m, mr) and torch.equal(i, ir), g
-        assert torch.equal(bns_a[g].running_mean, bns_b[g].running_mean), g
-        assert torch.equal(bns_a[g].running_var, bns_b[g].running_var), g
-
-
 def _dec_e5m2(y8):
     return y8.cpu().view(torch.float8_e5m2).double()
 
